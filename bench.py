@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- uvg266's per-CTU hot path on MI355X: closed-loop all-intra encode rate and the kernels under it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line: `value`, `ms_per_step`, `roofline` (from the HIP events
+of the timed steps).  --dump-outputs DIR also writes what the last timed step computed (dump_outputs).  Everything else below --
+the parity check against the reference encoder's record, extra_workloads, cpu_baseline, and with --gpus N > 1 row_sharded_rccl --
+runs only with --full.
 
 One "step" = one synthetic 1920x1080 8-bit yuv420p picture (BASELINE.json configs[1]: -p 1 --preset medium, QP 22), already
 resident in HBM, taken through the CLOSED loop the reference runs per CTU: uvghip_ctu_search_intra (one workgroup per CTU on
@@ -377,9 +382,14 @@ class ClosedLoop:
     (tests/test_gpu_sao_decide.py, tests/test_gpu_slice_coder.py)."""
 
     def __init__(self, wl, first_t, in_flight, device, step=1):
+        from concurrent.futures import ThreadPoolExecutor
         self.W, self.H, self.depth = wl["W"], wl["H"], wl["depth"]
         self.P = api.ctu_params(self.W, self.H, QP)
-        self.host = [layout.synthetic_yuv420(self.W, self.H, first_t + k * step, self.depth) for k in range(in_flight)]
+        self.ts = [first_t + k * step for k in range(in_flight)]
+        # a 1080p picture is ~0.1 s of numpy on one core and a group has hundreds: made side by side (numpy's array work releases
+        # the GIL; every picture has its own seeded generator, so the pictures are the same as one after the other)
+        with ThreadPoolExecutor(max(1, min(16, len(os.sched_getaffinity(0))))) as ex:
+            self.host = list(ex.map(lambda t: layout.synthetic_yuv420(self.W, self.H, t, self.depth), self.ts))
         src = [tuple(torch.from_numpy(np.ascontiguousarray(p)).to(device) for p in yuv) for yuv in self.host]
         self.cs = api.ClosedLoop(self.P, src)
         self.stream = torch.cuda.Stream(device=device)
@@ -401,6 +411,37 @@ class ClosedLoop:
 
     def search_ms(self):
         return sum(a.elapsed_time(b) for a, b in self.ev), len(self.ev)
+
+
+DUMP_BUDGET = 64_000_000            # bytes of .npy data that --dump-outputs may write
+
+
+def dump_outputs(group, out_dir):
+    """What the last timed step handed its caller -- the output pictures (after deblocking + SAO) and the slice data of every WPP row --
+    as out_dir/<name>.npy.  All of it would be gigabytes in float32, so: row_bytes of every picture of the step, and the whole output
+    pictures and slice data of a seeded sample of them (as many as fit in 40 MB, at least one; picture_t = their numbers in the synthetic
+    sequence).  The sample depends on the arguments only, so two builds of the project can be compared output for output."""
+    cs, n = group.cs, group.cs.n
+    per_picture = sum(p.numel() for p in cs.out[0]) * 4
+    k = max(1, min(n, int(40e6 // per_picture)))
+    pick = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+    torch.cuda.synchronize()
+    rows, nbytes = cs.slice_data()
+    nb = nbytes.cpu().numpy()
+    arrays = {"picture_t": np.array([group.ts[i] for i in pick], np.float64), "row_bytes": nb.astype(np.float64)}
+    for c, name in enumerate(("final_y", "final_u", "final_v")):
+        arrays[name] = np.stack([cs.out[i][c].cpu().numpy() for i in pick]).astype(np.float32)
+    data = []
+    for i in pick:                  # picture after picture, each one's rows in order (row_bytes splits them)
+        r = rows[i].cpu().numpy()
+        data += [r[j, :nb[i, j]] for j in range(nb.shape[1])]
+    arrays["slice_data"] = np.concatenate(data).astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET}-byte budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def alf_stage_timing(group, reps=2):
@@ -1291,8 +1332,14 @@ def main():
     ap.add_argument("--only-2160p", action="store_true", help="time only extra_workloads.2160p10_closed_loop (with its ALF stage) and print it (development)")
     ap.add_argument("--only-ra-clip", action="store_true", help="time only extra_workloads.ra_clip and print it (development)")
     ap.add_argument("--c3-sequences", type=int, default=96, help="extra_workloads.c3_low_delay_closed_loop: independent low-delay sequences side by side")
-    ap.add_argument("--no-extra", action="store_true", help="do not also time the 2160p 10-bit closed loop (extra_workloads)")
+    ap.add_argument("--no-extra", action="store_true", help="--full: do not also time the 2160p 10-bit closed loop (extra_workloads)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the judged line also run the parity check against the reference encoder's record, extra_workloads, cpu_baseline "
+                         "and (--gpus N > 1) row_sharded_rccl; a plain run times the judged line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1359,14 +1406,16 @@ def main():
     steps = args.steps
     cl, F, elapsed, search_ms, launches = closed_loop(wl, steps, args.warmup, args.in_flight, device, rank, world, dist, args.groups)
     n_groups = len(cl)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(cl[(steps - 1) % n_groups], args.dump_outputs)
     parity = None
-    if rank == 0 and not args.no_parity:
+    if args.full and rank == 0 and not args.no_parity:
         parity = [parity_check(cl[0], {"1080p8": "ref_ctucrc_1920x1080_8_qp22", "2160p10alf": "ref_ctucrc_3840x2160_10_qp22"}[wl_name])]
     del cl
     pics = steps * F * world
     fps = pics / elapsed
     extra = None
-    if not args.no_extra and wl_name == "1080p8":
+    if args.full and not args.no_extra and wl_name == "1080p8":
         ewl = WORKLOADS["2160p10alf"]
         ek, eF = 8, max(1, args.in_flight // 2)          # (a 4K picture has 93 diagonals of at most 34 CTUs: 112 pictures keep the 1024 workgroup slots fed)
         ecl, eF, eel, ems, eln = closed_loop(ewl, ek, 2, eF, device, rank, world, dist, args.groups)
@@ -1397,7 +1446,7 @@ def main():
         if alf_t is not None and "ms_per_group" in alf_t and alf_t.get("parity_checked"):
             extra["value_with_alf_stage"] = round(ek * eF * world / (eel + ek * alf_t["ms_per_group"] * 1e-3), 3)        # (sequential: nothing of the stage overlaps the loop)
     c3 = c3_loop = clip = c3_one = ra_one = c4_one = tiles_one = None
-    if not args.no_extra and wl_name == "1080p8" and rank == 0:
+    if args.full and not args.no_extra and wl_name == "1080p8" and rank == 0:
         def side(fn, *a, **k):          # a side workload must not take the judged line down with it
             try:
                 return fn(*a, **k)
@@ -1484,7 +1533,7 @@ def main():
                 out["open_loop"] = open_loop
             if row_sharded is not None:
                 out["row_sharded_rccl"] = row_sharded
-            if world == 1 and not args.no_cpu_baseline and wl_name == "1080p8":
+            if args.full and world == 1 and not args.no_cpu_baseline and wl_name == "1080p8":
                 dropin = {}
                 out["cpu_baseline"] = cpu_baseline_reference(wl, dropin=dropin) or cpu_baseline_search(wl)
                 if dropin:
@@ -1492,7 +1541,7 @@ def main():
             print(json.dumps(out), flush=True)
 
     row_sharded = None
-    if world > 1 and args.shard == "rows":
+    if args.full and world > 1 and args.shard == "rows":
         # The row-sharded RCCL plan is a secondary line and the only part of the run with data-path collectives on a device set this
         # code has never met: if it does not finish in time the judged line is still printed (by a watchdog) and the process ends.
         import threading
