@@ -966,8 +966,8 @@ UVGHIP_API int uvghip_loop_plan_create(int bitdepth, const uvghip_ctu_params_t *
                                        int n_pictures, int sao_type, void *workspace, uvghip_loop_plan_t **plan_out);
 UVGHIP_API int uvghip_loop_plan_run(uvghip_loop_plan_t *plan, void *stream);
 /* The same results with the three launches BESIDE each other instead of one after the other (the latency of ONE group: a clip, a picture):
- * the search on `stream`, the filter stage on a stream of the plan's own behind the search's per-CTU flags
- * (uvghip_filter_pictures_run_behind), the coder on another behind the filter stage's (uvghip_encode_slice_rows_behind) -- a CTU is
+ * the search on `stream`, the filter stage on a stream of the plan's own behind the search's per-CTU "searched" flags, the coder on
+ * another behind the filter stage's per-CTU "final" flags -- a CTU is
  * filtered when it is searched and coded when it is filtered, as encoder_state_worker_encode_lcu_search / _bitstream do CTU by CTU
  * (src/encoderstate.c:808-939), and the group's tail is one CTU's filter + its row's last bins instead of the whole filter and coder
  * launches.  Forked from and joined to `stream`.  What runs beside the search is capped (128 persistent filter workgroups, 256 persistent
@@ -999,10 +999,8 @@ UVGHIP_API void uvghip_loop_plan_destroy(uvghip_loop_plan_t *plan);
  * row_cap the buffer was too small and the row is truncated: 2 * 64 * pic_w * 1.5 bytes per row is a safe capacity).
  * The slice data of picture p is its rows one after the other; entry points = the row lengths.  One wave per row.
  * workspace: uvghip_slice_rows_workspace_bytes(n_pictures) of device memory; it receives the picture table (a synchronous
- * upload).  uvghip_slice_rows_prepare does only that; a later uvghip_encode_slice_rows with pictures == NULL reuses the table in the
- * workspace and just enqueues the kernel. */
+ * upload).  A later uvghip_encode_slice_rows with pictures == NULL reuses the table in the workspace and just enqueues the kernel. */
 UVGHIP_API size_t uvghip_slice_rows_workspace_bytes(int n_pictures);
-UVGHIP_API int uvghip_slice_rows_prepare(const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, int n_pictures, void *workspace);
 UVGHIP_API int uvghip_encode_slice_rows(int bitdepth, const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures,
                                         int n_pictures, const int32_t *sao_info, const uint16_t *sao_models, void *workspace,
                                         uint8_t *out, int row_cap, int32_t *row_bytes, void *stream);
@@ -1391,58 +1389,6 @@ typedef struct uvghip_ctu_pb_picture {
 UVGHIP_API size_t uvghip_ctu_search_pb_workspace_bytes(int n_pictures, int pic_w, int pic_h);
 UVGHIP_API int uvghip_ctu_search_pb(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, int n_pictures, void *workspace, void *stream);
 
-/* Pictures IN FLIGHT behind their references -- the encoder's --owf schedule (src/encoderstate.c:1060-1116: with cfg.owf != 0 the search
- * of CTU (x, y) of a picture waits for CTU (x + 2, y + 1) of its reference, clamped to the picture; encoder.c:244-245 max_inter_ref_lcu =
- * {1, 1}; its vectors stay inside what is final there, fracmv_within_tile src/search_inter.c:94-149 = inflight_margin).  The pictures of
- * ONE call may refer to each other: they are given in coding order, ref_in_call[i * 16 + k] = the index (< i) of the picture of this call
- * whose OUTPUT picture reference k of picture i is (its filters[].out_* planes and pictures[].motion_out), or -1 for a reference that is
- * complete before the call.  The device waits for less than the reference and for enough: CTU (x, y) starts when CTU (x + 1, y + 1) of
- * every reference inside the call is FINAL ((x + 2, y) in the last CTU row) -- under the vector restriction nothing beyond the CTUs
- * (x + 2 + j, y - j), j >= 0, and (x + 1, y + 1) can be read, and a CTU's "final" flag is raised after its left, upper and upper-right
- * neighbour's, so that one flag covers exactly that shape.  Same pictures, same stream, a shorter wait.
- * Every CTU runs its in-loop filters right behind its search inside the persistent kernel (what
- * encoder_state_worker_encode_lcu_search does after uvg_search_lcu, encoderstate.c:841-853): deblocking, uvg_sao_search_lcu's statistics
- * and decision, encoder_sao_reconstruct -- so the output picture becomes final CTU by CTU, and a per-CTU flag releases the CTUs of the
- * pictures behind.  pic.rec_* stay the UNFILTERED reconstruction (uvghip_loop_pb_run deblocks them in place); filters[i].dbk_* receive
- * the deblocked picture, out_* the picture uvg_encoder_encode returns (after SAO; sao_type 0: the deblocked picture), sao_info
- * [ctu][34] / sao_models [ctu][6] the decisions in uvghip_sao_decide_pictures_slice's layout.  Requirements beyond uvghip_ctu_search_pb:
- * params.qp == params.qp_c == frame_qp; a picture with a reference inside the call has inflight_margin = 11 (sao_type != 0) or 9.
- * Everything is enqueued on `stream` in stream order; nothing waits for the device.  The launch has four waves per CTU (the walk, the
- * 4x4 CUs of 8x8 areas, the 16x16 and the 32x32 CUs on a wave each, ahead of the walk: csrc/ctu_pb.h; UVGHIP_PB_WAVES=1..4 for
- * development) -- a CTU's latency, not the device's occupancy, sets the pace of dependent pictures. */
-typedef struct uvghip_pb_filter {
-  void *dbk_y, *dbk_u, *dbk_v;          /* DEVICE, pic_w x pic_h (+ chroma) */
-  void *out_y, *out_u, *out_v;
-  int32_t dbk_stride, dbk_stride_c, out_stride, out_stride_c;     /* in samples */
-  int32_t *sao_info;
-  uint16_t *sao_models;
-  int32_t sao_type, reserved;           /* cfg.sao_type: 0 off, 1 edge, 2 band, 3 both */
-} uvghip_pb_filter_t;
-UVGHIP_API size_t uvghip_ctu_search_pb_inflight_workspace_bytes(int n_pictures, int pic_w, int pic_h);
-UVGHIP_API int uvghip_ctu_search_pb_inflight(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, const uvghip_pb_filter_t *filters, const int32_t *ref_in_call,
-                                             int n_pictures, void *workspace, void *stream);
-
-/* The same filter stage as ONE launch over a group of searched pictures, a workgroup per CTU (csrc/filters.hip) -- what the loop plans
- * run behind the search instead of the chain of whole-picture kernels (snapshot deblocking, SAO statistics, decision, deblocking, SAO apply:
- * the same pictures, decisions and models).  pictures[i].rec_* / cu / src_*: the search's outputs (rec stays unfiltered), filters[i] as for
- * pictures in flight; slice_type 0 B / 1 P / 2 I (the SAO models' initialisation) and params->qp / lambda of the whole group.
- * prepare: the picture table into the workspace (synchronous, once); run: a memset of the flags + the launch, nothing waits. */
-UVGHIP_API size_t uvghip_filter_pictures_workspace_bytes(int n_pictures, int pic_w, int pic_h);
-UVGHIP_API int uvghip_filter_pictures_prepare(int bitdepth, const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, const uvghip_pb_filter_t *filters,
-                                              int n_pictures, int slice_type, void *workspace);
-UVGHIP_API int uvghip_filter_pictures_run(int bitdepth, int n_pictures, int pic_w, int pic_h, void *workspace, void *stream);
-/* ... BESIDE the search that feeds it instead of behind it: uvghip_filter_pictures_reset (ticket and flags to zero, in stream order), then on
- * a stream that waits for the reset uvghip_filter_pictures_run_behind -- at most max_workgroups persistent workgroups that take CTU after CTU in
- * wavefront order and wait for searched[picture][ctu] (the search plan's flags, uvghip_ctu_plan_done_flags) of each: a CTU is filtered as soon
- * as it is searched (the order of encoder_state_worker_encode_lcu_search, src/encoderstate.c:808-853, CTU by CTU).  The search must have been
- * LAUNCHED before this kernel (a waiting workgroup holds its slot; the cap keeps the device for the search).
- * uvghip_filter_pictures_final_flags: the stage's own per-CTU flags [picture][ctu] (device memory) -- 1 when the CTU's SAO decision and its
- * part of the output picture are published: what uvghip_encode_slice_rows_behind waits for. */
-UVGHIP_API int uvghip_filter_pictures_reset(int n_pictures, int pic_w, int pic_h, void *workspace, void *stream);
-UVGHIP_API int uvghip_filter_pictures_run_behind(int bitdepth, int n_pictures, int pic_w, int pic_h, void *workspace, const int32_t *searched, int max_workgroups,
-                                                 void *stream);
-UVGHIP_API const int32_t *uvghip_filter_pictures_final_flags(int n_pictures, int pic_w, int pic_h, const void *workspace);
-
 /* replaces, for a group of independent P / B pictures: the whole per-picture loop of the CTU worker (src/encoderstate.c:808-976) --
  * uvghip_ctu_search_pb, then per picture uvghip_deblock_frame_sao_snapshot on a copy of the reconstruction + uvghip_sao_stats_batch,
  * uvghip_sao_decide_pictures_slice (the picture's QP, lambda and slice type), uvghip_deblock_frame in place on rec (boundary strengths
@@ -1461,10 +1407,29 @@ UVGHIP_API int uvghip_loop_pb_run(int bitdepth, const uvghip_loop_pb_picture_t *
 UVGHIP_API int uvghip_loop_pb_results(int bitdepth, int n_pictures, int pic_w, int pic_h, void *workspace, const int32_t **sao_info,
                                       const uint16_t **sao_models, const uint8_t **rows, const int32_t **row_bytes, int *row_cap, int *n_rows);
 
-/* uvghip_loop_pb_run for pictures IN FLIGHT behind their references (uvghip_ctu_search_pb_inflight above: pictures in coding order,
- * ref_in_call[i * 16 + k]): one persistent launch for the search + the per-CTU in-loop filters of the whole reference DAG of the call,
- * then one launch of the arithmetic coder over all its pictures.  pic.rec_* stay unfiltered; the deblocked pictures live in the workspace.
- * Results as uvghip_loop_pb_results.  Nothing waits for the stream. */
+/* uvghip_loop_pb_run for pictures IN FLIGHT behind their references -- the encoder's --owf schedule (src/encoderstate.c:1060-1116: with
+ * cfg.owf != 0 the search of CTU (x, y) of a picture waits for CTU (x + 2, y + 1) of its reference, clamped to the picture;
+ * encoder.c:244-245 max_inter_ref_lcu = {1, 1}; its vectors stay inside what is final there, fracmv_within_tile src/search_inter.c:94-149
+ * = inflight_margin).  The pictures of ONE call may refer to each other: they are given in coding order, ref_in_call[i * 16 + k] = the
+ * index (< i) of the picture of this call whose OUTPUT picture reference k of picture i is (its out_* planes and search.motion_out), or -1
+ * for a reference that is complete before the call.  The device waits for less than the reference and for enough: CTU (x, y) starts when
+ * CTU (x + 1, y + 1) of every reference inside the call is FINAL ((x + 2, y) in the last CTU row) -- under the vector restriction nothing
+ * beyond the CTUs (x + 2 + j, y - j), j >= 0, and (x + 1, y + 1) can be read, and a CTU's "final" flag is raised after its left, upper and
+ * upper-right neighbour's, so that one flag covers exactly that shape.  Same pictures, same stream, a shorter wait.
+ * One persistent launch for the search of the whole reference DAG of the call, every CTU running its in-loop filters right behind its
+ * search (what encoder_state_worker_encode_lcu_search does after uvg_search_lcu, encoderstate.c:841-853: deblocking, uvg_sao_search_lcu's
+ * statistics and decision, encoder_sao_reconstruct), so that the output picture becomes final CTU by CTU and a per-CTU flag releases the
+ * CTUs of the pictures behind; then one launch of the arithmetic coder over all its pictures.  pic.rec_* stay unfiltered; the deblocked
+ * pictures live in the workspace; out_* receive the picture uvg_encoder_encode returns (after SAO; sao_type 0: the deblocked picture).
+ * Requirements beyond uvghip_ctu_search_pb: params.qp == params.qp_c == frame_qp; a picture with a reference inside the call has
+ * inflight_margin = 11 (sao_type != 0) or 9.  The search launch has four waves per CTU (the walk, the 4x4 CUs of 8x8 areas, the 16x16 and
+ * the 32x32 CUs on a wave each, ahead of the walk: csrc/ctu_pb.h; UVGHIP_PB_WAVES=1..4 for development) -- a CTU's latency, not the
+ * device's occupancy, sets the pace of dependent pictures.  Results as uvghip_loop_pb_results.  Nothing waits for the stream. */
+UVGHIP_API size_t uvghip_loop_pb_inflight_workspace_bytes(int bitdepth, int n_pictures, int pic_w, int pic_h);
+UVGHIP_API int uvghip_loop_pb_run_inflight(int bitdepth, const uvghip_loop_pb_picture_t *pictures, int n_pictures, int sao_type, const int32_t *ref_in_call,
+                                           void *workspace, void *stream);
+UVGHIP_API int uvghip_loop_pb_inflight_results(int bitdepth, int n_pictures, int pic_w, int pic_h, void *workspace, const int32_t **sao_info,
+                                               const uint16_t **sao_models, const uint8_t **rows, const int32_t **row_bytes, int *row_cap, int *n_rows);
 /* ... with I pictures IN the flight (round 6): a picture of the call whose SEARCH runs in the all-intra launch on ANOTHER stream beside this
  * call (ext[i].searched_flags = uvghip_loop_plan_searched_flags(plan) + picture * ctus; pictures[i].search.slice_type 2, .params / .pic the
  * plan's picture, out_* its output planes).  This call runs its filter stage CTU by CTU as that launch finishes its CTUs and the P / B
@@ -1474,7 +1439,7 @@ UVGHIP_API int uvghip_loop_pb_results(int bitdepth, int n_pictures, int pic_w, i
  * The caller's duties: (1) uvghip_loop_plan_search_reset on the plan's stream, an event behind it, THIS call's stream waits for the event
  * (the flags must be zero before this call's kernel can look at them), then uvghip_loop_plan_search_launch; (2) the plan's launch must be
  * small enough to run beside this call's workgroups, which take whole CUs: uvghip_loop_plan_set_search_grid(plan, G) makes it G persistent
- * workgroups, and other_workgroups = G here leaves them their CUs (G / 4).  ext == NULL: uvghip_loop_pb_run_inflight. */
+ * workgroups, and other_workgroups = G (0..512) here leaves them their CUs (G / 4).  ext == NULL: uvghip_loop_pb_run_inflight. */
 typedef struct uvghip_inflight_external {
   const int32_t *searched_flags;        /* DEVICE, [ctus]; NULL: an ordinary picture of the call */
   int32_t *sao_info;                    /* DEVICE, [ctus][34] / [ctus][6]: where the picture's SAO decisions go (NULL: the call's own results) */
@@ -1482,8 +1447,9 @@ typedef struct uvghip_inflight_external {
 } uvghip_inflight_external_t;
 UVGHIP_API int uvghip_loop_pb_run_inflight_ext(int bitdepth, const uvghip_loop_pb_picture_t *pictures, int n_pictures, int sao_type, const int32_t *ref_in_call,
                                                const uvghip_inflight_external_t *ext, int other_workgroups, void *workspace, void *stream);
-UVGHIP_API int uvghip_ctu_search_pb_inflight_ext(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, const uvghip_pb_filter_t *filters, const int32_t *ref_in_call,
-                                                 const int32_t *const *searched_flags, int other_workgroups, int n_pictures, void *workspace, void *stream);
+/* where the in-flight launch of a call on `workspace` raises its pictures' per-CTU "final" flags ([picture][ctu], device memory): 1 when the
+ * CTU's SAO decision and its part of the output picture are published.  The call zeroes them in its stream before its kernel. */
+UVGHIP_API const int32_t *uvghip_loop_pb_inflight_final_flags(int bitdepth, int n_pictures, int pic_w, int pic_h, const void *workspace);
 /* the all-intra plan's side of it: the search launch in two halves (reset: counters and flags to zero in stream order; launch), as G
  * persistent workgroups (0: one per CTU), its per-CTU "searched" flags [picture][ctu], and the slice data alone */
 UVGHIP_API int uvghip_loop_plan_search_reset(uvghip_loop_plan_t *plan, void *stream);
@@ -1495,29 +1461,8 @@ UVGHIP_API int uvghip_loop_plan_run_coder(uvghip_loop_plan_t *plan, void *stream
  * raises when a CTU's filters are done (final_flags: [picture][ctu] of the plan's pictures inside uvghip_loop_pb_inflight_final_flags of
  * the call, i.e. + first_picture * ctus), so the I pictures' slice data is written while the P / B pictures are still searched.  Enqueue
  * it behind uvghip_loop_plan_search_launch on the same stream (the search's outputs must be complete), and zero the flags of these
- * pictures in that stream before the search launch (the in-flight call zeroes all of them again in its own stream before its kernel).
- * uvghip_encode_slice_rows_behind is the same for a caller's own buffers (I slices, SAO on). */
+ * pictures in that stream before the search launch (the in-flight call zeroes all of them again in its own stream before its kernel). */
 UVGHIP_API int uvghip_loop_plan_run_coder_behind(uvghip_loop_plan_t *plan, const int32_t *final_flags, void *stream);
-UVGHIP_API int uvghip_encode_slice_rows_behind(int bitdepth, const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, int n_pictures,
-                                               const int32_t *sao_info, const uint16_t *sao_models, const int32_t *final_flags, void *workspace, uint8_t *out,
-                                               int row_cap, int32_t *row_bytes, void *stream);
-/* ... with at most max_waves rows in progress: persistent waves take row r of every picture, then row r + 1, from `ticket` (one int32 of DEVICE
- * memory, zeroed by the caller in stream order before this call) -- for a coder that runs beside a search that is STILL RUNNING, where a
- * waiting wave per row of a whole clip would hold the LDS the search needs (uvghip_loop_plan_run_overlapped). */
-UVGHIP_API int uvghip_encode_slice_rows_behind_capped(int bitdepth, const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, int n_pictures,
-                                                      const int32_t *sao_info, const uint16_t *sao_models, const int32_t *final_flags, int32_t *ticket, int max_waves,
-                                                      void *workspace, uint8_t *out, int row_cap, int32_t *row_bytes, void *stream);
-UVGHIP_API const int32_t *uvghip_loop_pb_inflight_final_flags(int bitdepth, int n_pictures, int pic_w, int pic_h, const void *workspace);
-UVGHIP_API const int32_t *uvghip_ctu_search_pb_inflight_final_flags(int n_pictures, int pic_w, int pic_h, const void *workspace);
-UVGHIP_API int uvghip_ctu_plan_reset(uvghip_ctu_plan_t *plan, void *stream);
-UVGHIP_API int uvghip_ctu_plan_launch(uvghip_ctu_plan_t *plan, void *stream);
-UVGHIP_API int uvghip_ctu_plan_set_grid(uvghip_ctu_plan_t *plan, int max_workgroups);
-UVGHIP_API const int32_t *uvghip_ctu_plan_done_flags(const uvghip_ctu_plan_t *plan);
-UVGHIP_API size_t uvghip_loop_pb_inflight_workspace_bytes(int bitdepth, int n_pictures, int pic_w, int pic_h);
-UVGHIP_API int uvghip_loop_pb_run_inflight(int bitdepth, const uvghip_loop_pb_picture_t *pictures, int n_pictures, int sao_type, const int32_t *ref_in_call,
-                                           void *workspace, void *stream);
-UVGHIP_API int uvghip_loop_pb_inflight_results(int bitdepth, int n_pictures, int pic_w, int pic_h, void *workspace, const int32_t **sao_info,
-                                               const uint16_t **sao_models, const uint8_t **rows, const int32_t **row_bytes, int *row_cap, int *n_rows);
 
 #ifdef __cplusplus
 }

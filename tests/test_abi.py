@@ -38,6 +38,27 @@ def test_ctypes_table_matches_header():
     assert sorted(lib.SIGNATURES) == header_symbols()
 
 
+def internal_symbols():
+    src = open(os.path.join(ROOT, "uvg266_amd", "csrc", "internal.h")).read()
+    return sorted(set(re.findall(r"\b(uvgi_\w+)\s*\(", src)))
+
+
+def test_internal_steps_stay_out_of_the_abi():
+    """uvg266_amd/csrc/internal.h declares the steps the library's files call in each other (launch halves and flags whose
+    stream-order duties nothing checks): none of them is declared in the public header, listed in the ctypes table or exported,
+    under its own name or a mangled one."""
+    from uvg266_amd import lib
+    names = internal_symbols()
+    assert "uvgi_ctu_plan_launch" in names and "uvgi_search_pb_inflight" in names
+    assert not set(names) & set(header_symbols())
+    assert not set(names) & set(lib.SIGNATURES)
+    lib.load_library()
+    out = subprocess.check_output(["nm", "-D", "--defined-only", lib.LIB_PATH], text=True)
+    exported = [line.split()[-1] for line in out.splitlines()]
+    leaked = [n for n in names if any(n in s for s in exported)]
+    assert not leaked, f"declared in csrc/internal.h but exported: {leaked}"
+
+
 def test_no_cpu_fallback_without_device():
     import torch
     if torch.cuda.is_available():

@@ -26,7 +26,7 @@ int uvghip_set_error(hipError_t e, const char *where)
 bool uvghip_ready() { return g_ready.load(std::memory_order_acquire) != 0; }
 
 extern "C" const char *uvghip_last_error(void) { return t_err; }
-extern "C" int uvghip_abi_version(void) { return 1; }
+extern "C" int uvghip_abi_version(void) { return 2; }
 
 extern "C" int uvghip_init(int device)
 {

@@ -41,7 +41,7 @@ struct launch_args {
 static_assert(sizeof(ctu::lds<uint8_t>) + 4304 <= 40960, "the 8-bit LDS image of a CTU no longer fits four workgroups per CU");
 static_assert(!ctu::lds_cfg<uint16_t>::slim || sizeof(ctu::lds<uint16_t>) + 4304 <= 40960, "the slim 10-bit LDS image of a CTU no longer fits four workgroups per CU");
 
-// PERSIST: a small grid of workgroups that take CTU after CTU (uvghip_ctu_plan_set_grid) -- for a few pictures whose search runs BESIDE
+// PERSIST: a small grid of workgroups that take CTU after CTU (uvgi_ctu_plan_set_grid) -- for a few pictures whose search runs BESIDE
 // another kernel (the I pictures of a clip beside the in-flight P / B launch, which takes whole CUs): the launch then holds G workgroup
 // slots instead of one per CTU, most of them waiting.  Same CTUs, same order, same results.
 template <typename PX, bool PERSIST>
@@ -183,7 +183,7 @@ extern "C" size_t uvghip_ctu_search_workspace_bytes(int n_pictures, int pic_w, i
 struct uvghip_ctu_plan {
   launch_args A;
   int bitdepth, total;
-  int grid;                   // 0: a workgroup per CTU; else that many persistent workgroups (uvghip_ctu_plan_set_grid)
+  int grid;                   // 0: a workgroup per CTU; else that many persistent workgroups (uvgi_ctu_plan_set_grid)
   size_t counters;            // bytes of (ticket, done flags) at the head of the workspace
   unsigned char *ws;
 };
@@ -267,17 +267,14 @@ extern "C" int uvghip_ctu_plan_create_rows(int bitdepth, const uvghip_ctu_params
   return 0;
 }
 
-// A run in two halves, for a caller that lets ANOTHER stream's kernel wait for this plan's per-CTU flags (pictures in flight behind an I
-// picture, uvghip_loop_pb_run_inflight_ext): reset -- the counters and flags back to zero, in stream order; the other stream waits for
-// an event recorded behind it -- then launch.  uvghip_ctu_plan_run is the two in a row.
-extern "C" int uvghip_ctu_plan_reset(uvghip_ctu_plan_t *pl, void *stream)
+int uvgi_ctu_plan_reset(uvghip_ctu_plan_t *pl, void *stream)
 {
   UVGHIP_REQUIRE_READY();
   if (!pl) return uvghip_set_error(hipErrorInvalidValue, __func__);
   UVGHIP_TRY(hipMemsetAsync(pl->ws, 0, pl->counters, uvghip_stream(stream)));
   return 0;
 }
-extern "C" int uvghip_ctu_plan_launch(uvghip_ctu_plan_t *pl, void *stream)
+int uvgi_ctu_plan_launch(uvghip_ctu_plan_t *pl, void *stream)
 {
   UVGHIP_REQUIRE_READY();
   if (!pl) return uvghip_set_error(hipErrorInvalidValue, __func__);
@@ -294,18 +291,16 @@ extern "C" int uvghip_ctu_plan_launch(uvghip_ctu_plan_t *pl, void *stream)
 }
 extern "C" int uvghip_ctu_plan_run(uvghip_ctu_plan_t *pl, void *stream)
 {
-  if (int rc = uvghip_ctu_plan_reset(pl, stream)) return rc;
-  return uvghip_ctu_plan_launch(pl, stream);
+  if (int rc = uvgi_ctu_plan_reset(pl, stream)) return rc;
+  return uvgi_ctu_plan_launch(pl, stream);
 }
-// ... max_workgroups > 0: the launch is that many persistent workgroups (0: one per CTU, the default)
-extern "C" int uvghip_ctu_plan_set_grid(uvghip_ctu_plan_t *pl, int max_workgroups)
+int uvgi_ctu_plan_set_grid(uvghip_ctu_plan_t *pl, int max_workgroups)
 {
   if (!pl || max_workgroups < 0) return uvghip_set_error(hipErrorInvalidValue, __func__);
   pl->grid = max_workgroups;
   return 0;
 }
-// ... the per-CTU "searched" flags [picture][ctu] (DEVICE memory; zero after the reset, 1 when the CTU's outputs are published)
-extern "C" const int32_t *uvghip_ctu_plan_done_flags(const uvghip_ctu_plan_t *pl) { return pl ? pl->A.done : nullptr; }
+const int32_t *uvgi_ctu_plan_done_flags(const uvghip_ctu_plan_t *pl) { return pl ? pl->A.done : nullptr; }
 
 extern "C" void uvghip_ctu_plan_destroy(uvghip_ctu_plan_t *pl) { delete pl; }
 

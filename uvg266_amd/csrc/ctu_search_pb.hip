@@ -25,7 +25,7 @@ struct pb_pic_dev {
   int16_t *coeff;
   uint32_t *models, *models_inter;
   int src_stride, src_stride_c, rec_stride, rec_stride_c, cu_stride, pad;
-  // pictures in flight (uvghip_ctu_search_pb_inflight): the pictures of this call whose output this one reads, its depth in that DAG
+  // pictures in flight (uvgi_search_pb_inflight): the pictures of this call whose output this one reads, its depth in that DAG
   int n_wait, level;
   int wait_pic[16];
   // a picture whose SEARCH runs elsewhere (an I picture in the all-intra launch beside this call): its per-CTU "searched" flags; the
@@ -257,9 +257,7 @@ ws_layout layout(int n_pictures, int pic_w, int pic_h)
 
 }  // namespace
 
-// where the in-flight launch raises a picture's per-CTU "final" flags (picture i at [i * ctus]): a consumer of the finished pictures that runs
-// beside the launch waits on them (uvghip_loop_plan_run_coder_behind).  The launch zeroes them in stream order before its kernel.
-extern "C" const int32_t *uvghip_ctu_search_pb_inflight_final_flags(int n_pictures, int pic_w, int pic_h, const void *workspace)
+const int32_t *uvgi_search_pb_inflight_final_flags(int n_pictures, int pic_w, int pic_h, const void *workspace)
 {
   if (n_pictures <= 0 || pic_w <= 0 || pic_h <= 0 || !workspace) return nullptr;
   return reinterpret_cast<const int32_t *>(static_cast<const unsigned char *>(workspace) + layout(n_pictures, pic_w, pic_h).final_done);
@@ -284,29 +282,22 @@ extern "C" size_t uvghip_ctu_search_pb_workspace_bytes(int n_pictures, int pic_w
 }
 
 namespace {
-int search_pb(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, int n_pictures, const uvghip_pb_filter_t *filters, const int32_t *ref_in_call,
+int search_pb(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, int n_pictures, const uvgi_pb_filter *filters, const int32_t *ref_in_call,
               const int32_t *const *searched_flags, int other_workgroups, void *workspace, void *stream);
 }
 extern "C" int uvghip_ctu_search_pb(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, int n_pictures, void *workspace, void *stream)
 {
   return search_pb(bitdepth, pictures, n_pictures, nullptr, nullptr, nullptr, 0, workspace, stream);
 }
-extern "C" size_t uvghip_ctu_search_pb_inflight_workspace_bytes(int n_pictures, int pic_w, int pic_h) { return uvghip_ctu_search_pb_workspace_bytes(n_pictures, pic_w, pic_h); }
-extern "C" int uvghip_ctu_search_pb_inflight(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, const uvghip_pb_filter_t *filters, const int32_t *ref_in_call,
-                                             int n_pictures, void *workspace, void *stream)
+int uvgi_search_pb_inflight(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, const uvgi_pb_filter *filters, const int32_t *ref_in_call,
+                            const int32_t *const *searched_flags, int other_workgroups, int n_pictures, void *workspace, void *stream)
 {
-  if (!filters || !ref_in_call) return uvghip_set_error(hipErrorInvalidValue, __func__);
-  return search_pb(bitdepth, pictures, n_pictures, filters, ref_in_call, nullptr, 0, workspace, stream);
-}
-extern "C" int uvghip_ctu_search_pb_inflight_ext(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, const uvghip_pb_filter_t *filters, const int32_t *ref_in_call,
-                                                 const int32_t *const *searched_flags, int other_workgroups, int n_pictures, void *workspace, void *stream)
-{
-  if (!filters || !ref_in_call || !searched_flags || other_workgroups < 0 || other_workgroups > 512) return uvghip_set_error(hipErrorInvalidValue, __func__);
+  if (!filters || !ref_in_call || other_workgroups < 0 || other_workgroups > 512 || (!searched_flags && other_workgroups)) return uvghip_set_error(hipErrorInvalidValue, __func__);
   return search_pb(bitdepth, pictures, n_pictures, filters, ref_in_call, searched_flags, other_workgroups, workspace, stream);
 }
 
 namespace {
-int search_pb(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, int n_pictures, const uvghip_pb_filter_t *filters, const int32_t *ref_in_call,
+int search_pb(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, int n_pictures, const uvgi_pb_filter *filters, const int32_t *ref_in_call,
               const int32_t *const *searched_flags, int other_workgroups, void *workspace, void *stream)
 {
   UVGHIP_REQUIRE_READY();
@@ -329,15 +320,15 @@ int search_pb(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, int n_pictu
         p.qp_c < 0 || p.qp_c > 63 || !(p.lambda > 0) || !(p.lambda_sqrt > 0) || p.rd < 0 || p.rd > 1)
       return uvghip_set_error(hipErrorInvalidValue, "uvghip_ctu_search_pb: configuration outside the supported subset");
     if (searched_flags && searched_flags[i]) {
-      // a picture searched elsewhere (an I picture in uvghip_ctu_plan_launch beside this call): the filter stage only, behind that launch's flags
+      // a picture searched elsewhere (an I picture in uvgi_ctu_plan_launch beside this call): the filter stage only, behind that launch's flags
       const uvghip_ctu_picture_t &c = q.pic;
       if (!filters || !c.src_y || !c.src_u || !c.src_v || !c.rec_y || !c.rec_u || !c.rec_v || !c.cu || c.cu_stride < wc * 16 || c.src_stride < p.pic_w || c.rec_stride < p.pic_w ||
           c.src_stride_c < p.pic_w / 2 || c.rec_stride_c < p.pic_w / 2 || q.slice_type != 2 || p.qp_c != p.qp)
-        return uvghip_set_error(hipErrorInvalidValue, "uvghip_ctu_search_pb_inflight_ext: an externally searched picture");
-      const uvghip_pb_filter_t &f = filters[i];
+        return uvghip_set_error(hipErrorInvalidValue, "uvgi_search_pb_inflight: an externally searched picture");
+      const uvgi_pb_filter &f = filters[i];
       if (!f.dbk_y || !f.dbk_u || !f.dbk_v || !f.out_y || !f.out_u || !f.out_v || f.dbk_stride < p.pic_w || f.dbk_stride_c < p.pic_w / 2 || f.out_stride < p.pic_w ||
           f.out_stride_c < p.pic_w / 2 || f.sao_type < 0 || f.sao_type > 3 || (f.sao_type && (!f.sao_info || !f.sao_models)))
-        return uvghip_set_error(hipErrorInvalidValue, "uvghip_ctu_search_pb_inflight_ext: filter stage");
+        return uvghip_set_error(hipErrorInvalidValue, "uvgi_search_pb_inflight: filter stage");
       pb_pic_dev &d = pics[i];
       memset(&d, 0, sizeof d);
       memcpy(&d.P, &p, sizeof d.P);
@@ -386,23 +377,23 @@ int search_pb(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, int n_pictu
     d.src_stride = c.src_stride; d.src_stride_c = c.src_stride_c; d.rec_stride = c.rec_stride; d.rec_stride_c = c.rec_stride_c; d.cu_stride = c.cu_stride;
     if (filters) {
       // the picture's references inside this call (pictures are in coding order: a reference is an earlier entry), its depth in that DAG
-      const uvghip_pb_filter_t &f = filters[i];
+      const uvgi_pb_filter &f = filters[i];
       if (!f.dbk_y || !f.dbk_u || !f.dbk_v || !f.out_y || !f.out_u || !f.out_v || f.dbk_stride < p.pic_w || f.dbk_stride_c < p.pic_w / 2 || f.out_stride < p.pic_w ||
           f.out_stride_c < p.pic_w / 2 || f.sao_type < 0 || f.sao_type > 3 || (f.sao_type && (!f.sao_info || !f.sao_models)))
-        return uvghip_set_error(hipErrorInvalidValue, "uvghip_ctu_search_pb_inflight: filter stage");
-      if (p.qp_c != p.qp || p.qp != q.frame_qp) return uvghip_set_error(hipErrorInvalidValue, "uvghip_ctu_search_pb_inflight: qp_c != qp or params.qp != frame_qp");
+        return uvghip_set_error(hipErrorInvalidValue, "uvgi_search_pb_inflight: filter stage");
+      if (p.qp_c != p.qp || p.qp != q.frame_qp) return uvghip_set_error(hipErrorInvalidValue, "uvgi_search_pb_inflight: qp_c != qp or params.qp != frame_qp");
       d.n_wait = 0; d.level = 0;
       for (int k = 0; k < q.n_refs; ++k) {
         const int r = ref_in_call[(size_t)i * 16 + k];
         if (r < 0) continue;
-        if (r >= i) return uvghip_set_error(hipErrorInvalidValue, "uvghip_ctu_search_pb_inflight: a reference inside the call must be an earlier picture of it");
-        const uvghip_pb_filter_t &fr = filters[r];
+        if (r >= i) return uvghip_set_error(hipErrorInvalidValue, "uvgi_search_pb_inflight: a reference inside the call must be an earlier picture of it");
+        const uvgi_pb_filter &fr = filters[r];
         const bool r_ext = searched_flags && searched_flags[r];          // (an I picture: its motion table is the caller's constant "intra everywhere")
         if (q.ref_y[k] != fr.out_y || q.ref_u[k] != fr.out_u || q.ref_v[k] != fr.out_v || (!r_ext && q.ref_motion[k] != pictures[r].motion_out) || q.ref_stride != fr.out_stride ||
             q.ref_stride_c != fr.out_stride_c)
-          return uvghip_set_error(hipErrorInvalidValue, "uvghip_ctu_search_pb_inflight: ref_in_call names a picture whose output is not this reference");
+          return uvghip_set_error(hipErrorInvalidValue, "uvgi_search_pb_inflight: ref_in_call names a picture whose output is not this reference");
         // a reference still being coded: the vectors must stay inside what is final in it (fracmv_within_tile's margin: 1 + the filters' delay)
-        if (q.inflight_margin != (fr.sao_type ? 11 : 9)) return uvghip_set_error(hipErrorInvalidValue, "uvghip_ctu_search_pb_inflight: inflight_margin must be 11 (SAO) / 9 with a reference in flight");
+        if (q.inflight_margin != (fr.sao_type ? 11 : 9)) return uvghip_set_error(hipErrorInvalidValue, "uvgi_search_pb_inflight: inflight_margin must be 11 (SAO) / 9 with a reference in flight");
         bool seen = false;
         for (int j = 0; j < d.n_wait; ++j) seen = seen || d.wait_pic[j] == r;
         if (!seen) d.wait_pic[d.n_wait++] = r;

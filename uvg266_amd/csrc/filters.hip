@@ -1,4 +1,4 @@
-// uvghip_filter_pictures: the in-loop filters of a whole group of searched pictures in ONE launch -- a workgroup per CTU runs the per-CTU
+// uvgi_filter_*: the in-loop filters of a whole group of searched pictures in ONE launch -- a workgroup per CTU runs the per-CTU
 // filter stage of ctu_filter.h (deblocking of what the CTU completes, its SAO statistics and decision, SAO into the output picture: what
 // encoder_state_worker_encode_lcu_search does after uvg_search_lcu, src/encoderstate.c:841-853, with the pictures' reconstruction left
 // unfiltered).  It replaces the chain of whole-picture kernels the loop plans strung behind the search (per picture: three snapshot
@@ -29,7 +29,7 @@ struct filter_args {
   const fpic_dev *pics;
   int32_t *ticket, *sao_done, *final_done;
   int wc, hc, n_pictures, W, H;
-  const int32_t *searched;      // BEHIND: [picture][ctu], the search's "done" flags (uvghip_ctu_plan_done_flags)
+  const int32_t *searched;      // BEHIND: [picture][ctu], the search's "done" flags (uvgi_ctu_plan_done_flags)
 };
 
 // BEHIND: a small grid of persistent workgroups that take CTU after CTU and wait for the SEARCH's flag of each -- the filters of a group
@@ -88,34 +88,34 @@ fl_layout layout(int n, int w, int h)
 
 }  // namespace
 
-extern "C" size_t uvghip_filter_pictures_workspace_bytes(int n_pictures, int pic_w, int pic_h)
+size_t uvgi_filter_workspace_bytes(int n_pictures, int pic_w, int pic_h)
 {
   if (n_pictures <= 0 || pic_w <= 0 || pic_h <= 0) return 0;
   return layout(n_pictures, pic_w, pic_h).total;
 }
 
-// The picture table is written once per workspace (prepare: synchronous copy, as uvghip_slice_rows_prepare), a run is a memset of the
+// The picture table is written once per workspace (prepare: synchronous copy, as the slice coder's table), a run is a memset of the
 // flags and one launch.
-extern "C" int uvghip_filter_pictures_prepare(int bitdepth, const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, const uvghip_pb_filter_t *filters,
-                                              int n_pictures, int slice_type, void *workspace)
+int uvgi_filter_prepare(int bitdepth, const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, const uvgi_pb_filter *filters, int n_pictures,
+                        int slice_type, void *workspace)
 {
   UVGHIP_REQUIRE_READY();
   UVGHIP_REQUIRE_DEPTH(bitdepth);
   if (!params || !pictures || !filters || n_pictures <= 0 || !workspace || slice_type < 0 || slice_type > 2) return uvghip_set_error(hipErrorInvalidValue, __func__);
   const int w = params->pic_w, h = params->pic_h;
-  if (w <= 0 || h <= 0 || (w & 7) || (h & 7)) return uvghip_set_error(hipErrorInvalidValue, "uvghip_filter_pictures_prepare: picture size");
-  if (params->qp_c != params->qp) return uvghip_set_error(hipErrorInvalidValue, "uvghip_filter_pictures_prepare: qp_c != qp needs a chroma QP table");
+  if (w <= 0 || h <= 0 || (w & 7) || (h & 7)) return uvghip_set_error(hipErrorInvalidValue, "uvgi_filter_prepare: picture size");
+  if (params->qp_c != params->qp) return uvghip_set_error(hipErrorInvalidValue, "uvgi_filter_prepare: qp_c != qp needs a chroma QP table");
   const int wc = (w + 63) / 64;
   std::vector<fpic_dev> pd(n_pictures);
   for (int i = 0; i < n_pictures; ++i) {
     const uvghip_ctu_picture_t &p = pictures[i];
-    const uvghip_pb_filter_t &f = filters[i];
+    const uvgi_pb_filter &f = filters[i];
     if (!p.src_y || !p.src_u || !p.src_v || !p.rec_y || !p.rec_u || !p.rec_v || !p.cu || p.cu_stride < wc * 16 || p.src_stride < w || p.rec_stride < w ||
         p.src_stride_c < w / 2 || p.rec_stride_c < w / 2)
-      return uvghip_set_error(hipErrorInvalidValue, "uvghip_filter_pictures_prepare: picture descriptor");
+      return uvghip_set_error(hipErrorInvalidValue, "uvgi_filter_prepare: picture descriptor");
     if (!f.dbk_y || !f.dbk_u || !f.dbk_v || !f.out_y || !f.out_u || !f.out_v || f.dbk_stride < w || f.dbk_stride_c < w / 2 || f.out_stride < w || f.out_stride_c < w / 2 ||
         f.sao_type < 0 || f.sao_type > 3 || (f.sao_type && (!f.sao_info || !f.sao_models)))
-      return uvghip_set_error(hipErrorInvalidValue, "uvghip_filter_pictures_prepare: filter stage");
+      return uvghip_set_error(hipErrorInvalidValue, "uvgi_filter_prepare: filter stage");
     fpic_dev &d = pd[i];
     ctuf::filt_pic &g = d.F;
     g.dbk_y = f.dbk_y; g.dbk_u = f.dbk_u; g.dbk_v = f.dbk_v; g.out_y = f.out_y; g.out_u = f.out_u; g.out_v = f.out_v;
@@ -130,30 +130,30 @@ extern "C" int uvghip_filter_pictures_prepare(int bitdepth, const uvghip_ctu_par
   return 0;
 }
 
-// The run in two halves for a caller that lets the stage run BESIDE the search that feeds it (and a coder behind the stage's own flags):
-// reset -- ticket and flags to zero, in stream order -- then uvghip_filter_pictures_run_behind on a stream that waits for the reset: at most
-// max_workgroups persistent workgroups, each CTU waiting for searched[picture][ctu] (the search plan's flags).
-extern "C" int uvghip_filter_pictures_reset(int n_pictures, int pic_w, int pic_h, void *workspace, void *stream)
+int uvgi_filter_reset(int n_pictures, int pic_w, int pic_h, void *workspace, void *stream)
 {
   UVGHIP_REQUIRE_READY();
   if (n_pictures <= 0 || pic_w <= 0 || pic_h <= 0 || !workspace) return uvghip_set_error(hipErrorInvalidValue, __func__);
   UVGHIP_TRY(hipMemsetAsync(workspace, 0, layout(n_pictures, pic_w, pic_h).pics, uvghip_stream(stream)));
   return 0;
 }
-// ... the stage's per-CTU "final" flags [picture][ctu] (DEVICE memory): 1 when the CTU's part of the output picture and its SAO decision are published
-extern "C" const int32_t *uvghip_filter_pictures_final_flags(int n_pictures, int pic_w, int pic_h, const void *workspace)
+const int32_t *uvgi_filter_final_flags(int n_pictures, int pic_w, int pic_h, const void *workspace)
 {
   if (n_pictures <= 0 || pic_w <= 0 || pic_h <= 0 || !workspace) return nullptr;
   return reinterpret_cast<const int32_t *>(static_cast<const unsigned char *>(workspace) + layout(n_pictures, pic_w, pic_h).final_done);
 }
-extern "C" int uvghip_filter_pictures_run_behind(int bitdepth, int n_pictures, int pic_w, int pic_h, void *workspace, const int32_t *searched, int max_workgroups, void *stream)
+
+// searched == NULL: the flags to zero here and a workgroup per CTU; else at most max_workgroups persistent workgroups behind the search's
+// flags, the flags zeroed beforehand by uvgi_filter_reset
+int uvgi_filter_run(int bitdepth, int n_pictures, int pic_w, int pic_h, void *workspace, const int32_t *searched, int max_workgroups, void *stream)
 {
   UVGHIP_REQUIRE_READY();
   UVGHIP_REQUIRE_DEPTH(bitdepth);
-  if (n_pictures <= 0 || pic_w <= 0 || pic_h <= 0 || !workspace || !searched || max_workgroups < 1) return uvghip_set_error(hipErrorInvalidValue, __func__);
+  if (n_pictures <= 0 || pic_w <= 0 || pic_h <= 0 || !workspace || (searched && max_workgroups < 1)) return uvghip_set_error(hipErrorInvalidValue, __func__);
   const fl_layout L = layout(n_pictures, pic_w, pic_h);
   unsigned char *ws = static_cast<unsigned char *>(workspace);
   hipStream_t st = uvghip_stream(stream);
+  if (!searched) UVGHIP_TRY(hipMemsetAsync(ws, 0, L.pics, st));
   filter_args A;
   A.pics = reinterpret_cast<const fpic_dev *>(ws + L.pics);
   A.ticket = reinterpret_cast<int32_t *>(ws + L.ticket);
@@ -161,30 +161,14 @@ extern "C" int uvghip_filter_pictures_run_behind(int bitdepth, int n_pictures, i
   A.final_done = reinterpret_cast<int32_t *>(ws + L.final_done);
   A.wc = (pic_w + 63) / 64; A.hc = (pic_h + 63) / 64; A.n_pictures = n_pictures; A.W = pic_w; A.H = pic_h;
   A.searched = searched;
-  const int total = A.wc * A.hc * n_pictures, grid = total < max_workgroups ? total : max_workgroups;
-  if (bitdepth == 8) hipLaunchKernelGGL((ctu_filter_kernel<uint8_t, true>), dim3(grid), dim3(256), sizeof(ctuf::filt_lds<uint8_t>), st, A);
-  else hipLaunchKernelGGL((ctu_filter_kernel<uint16_t, true>), dim3(grid), dim3(256), sizeof(ctuf::filt_lds<uint16_t>), st, A);
-  UVGHIP_CHECK_LAUNCH();
-}
-
-extern "C" int uvghip_filter_pictures_run(int bitdepth, int n_pictures, int pic_w, int pic_h, void *workspace, void *stream)
-{
-  UVGHIP_REQUIRE_READY();
-  UVGHIP_REQUIRE_DEPTH(bitdepth);
-  if (n_pictures <= 0 || pic_w <= 0 || pic_h <= 0 || !workspace) return uvghip_set_error(hipErrorInvalidValue, __func__);
-  const fl_layout L = layout(n_pictures, pic_w, pic_h);
-  unsigned char *ws = static_cast<unsigned char *>(workspace);
-  hipStream_t st = uvghip_stream(stream);
-  UVGHIP_TRY(hipMemsetAsync(ws, 0, L.pics, st));
-  filter_args A;
-  A.searched = nullptr;
-  A.pics = reinterpret_cast<const fpic_dev *>(ws + L.pics);
-  A.ticket = reinterpret_cast<int32_t *>(ws + L.ticket);
-  A.sao_done = reinterpret_cast<int32_t *>(ws + L.sao_done);
-  A.final_done = reinterpret_cast<int32_t *>(ws + L.final_done);
-  A.wc = (pic_w + 63) / 64; A.hc = (pic_h + 63) / 64; A.n_pictures = n_pictures; A.W = pic_w; A.H = pic_h;
-  const int grid = A.wc * A.hc * n_pictures;
-  if (bitdepth == 8) hipLaunchKernelGGL((ctu_filter_kernel<uint8_t, false>), dim3(grid), dim3(256), sizeof(ctuf::filt_lds<uint8_t>), st, A);
-  else hipLaunchKernelGGL((ctu_filter_kernel<uint16_t, false>), dim3(grid), dim3(256), sizeof(ctuf::filt_lds<uint16_t>), st, A);
+  const int total = A.wc * A.hc * n_pictures;
+  if (searched) {
+    const int grid = total < max_workgroups ? total : max_workgroups;
+    if (bitdepth == 8) hipLaunchKernelGGL((ctu_filter_kernel<uint8_t, true>), dim3(grid), dim3(256), sizeof(ctuf::filt_lds<uint8_t>), st, A);
+    else hipLaunchKernelGGL((ctu_filter_kernel<uint16_t, true>), dim3(grid), dim3(256), sizeof(ctuf::filt_lds<uint16_t>), st, A);
+  } else {
+    if (bitdepth == 8) hipLaunchKernelGGL((ctu_filter_kernel<uint8_t, false>), dim3(total), dim3(256), sizeof(ctuf::filt_lds<uint8_t>), st, A);
+    else hipLaunchKernelGGL((ctu_filter_kernel<uint16_t, false>), dim3(total), dim3(256), sizeof(ctuf::filt_lds<uint16_t>), st, A);
+  }
   UVGHIP_CHECK_LAUNCH();
 }

@@ -1,0 +1,100 @@
+// The steps that one .hip file of the library calls in another: the launch halves and flags of the loop plans' search, filter and
+// coder launches.  Not part of the C ABI -- plain C++ linkage and no UVGHIP_API, so -fvisibility=hidden keeps them out of
+// libuvg266hip.so.  Their contracts (what must be zeroed in stream order first, what must already be LAUNCHED) are the callers' duty:
+// loop_plan.hip, loop_pb.hip and the public entry points of the files that define them.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <cstring>
+#include "../../include/uvg266_hip.h"
+
+// ---- ctu_search.hip: an all-intra search plan's run in two halves ------------------------------------------------------------------
+// For a caller that lets ANOTHER stream's kernel wait for this plan's per-CTU flags (pictures in flight behind an I picture,
+// uvghip_loop_pb_run_inflight_ext): reset -- the counters and flags back to zero, in stream order; the other stream waits for an event
+// recorded behind it -- then launch.  uvghip_ctu_plan_run is the two in a row.
+int uvgi_ctu_plan_reset(uvghip_ctu_plan_t *pl, void *stream);
+int uvgi_ctu_plan_launch(uvghip_ctu_plan_t *pl, void *stream);
+// ... max_workgroups > 0: the launch is that many persistent workgroups (0: one per CTU, the default)
+int uvgi_ctu_plan_set_grid(uvghip_ctu_plan_t *pl, int max_workgroups);
+// ... the per-CTU "searched" flags [picture][ctu] (DEVICE memory; zero after the reset, 1 when the CTU's outputs are published)
+const int32_t *uvgi_ctu_plan_done_flags(const uvghip_ctu_plan_t *pl);
+
+// ---- the per-CTU in-loop filter stage (ctu_filter.h): where a picture's filtered planes and SAO decisions go ---------------------------
+// dbk_*: the deblocked picture; out_*: the picture uvg_encoder_encode returns (after SAO; sao_type 0: the deblocked picture); sao_info
+// [ctu][34] / sao_models [ctu][6]: the decisions in uvghip_sao_decide_pictures_slice's layout.  The search's pic.rec_* stay unfiltered.
+struct uvgi_pb_filter {
+  void *dbk_y, *dbk_u, *dbk_v;          // DEVICE, pic_w x pic_h (+ chroma)
+  void *out_y, *out_u, *out_v;
+  int32_t dbk_stride, dbk_stride_c, out_stride, out_stride_c;     // in samples
+  int32_t *sao_info;
+  uint16_t *sao_models;
+  int32_t sao_type, reserved;           // cfg.sao_type: 0 off, 1 edge, 2 band, 3 both
+};
+
+// ---- filters.hip: the filter stage as ONE launch over a group of searched pictures, a workgroup per CTU -------------------------------
+// What the all-intra loop plan runs behind its search instead of the chain of whole-picture kernels (snapshot deblocking, SAO statistics,
+// decision, deblocking, SAO apply: the same pictures, decisions and models).  pictures[i].rec_* / cu / src_*: the search's outputs,
+// filters[i] as above; slice_type 0 B / 1 P / 2 I (the SAO models' initialisation) and params->qp / lambda of the whole group.
+// prepare: the picture table into the workspace (synchronous, once).
+size_t uvgi_filter_workspace_bytes(int n_pictures, int pic_w, int pic_h);
+int uvgi_filter_prepare(int bitdepth, const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, const uvgi_pb_filter *filters, int n_pictures,
+                        int slice_type, void *workspace);
+// run, searched == NULL: BEHIND the search -- a memset of the ticket and flags, then a workgroup per CTU; nothing waits.
+// run, searched != NULL: BESIDE the search that feeds it -- uvgi_filter_reset (ticket and flags to zero, in stream order) first, then this on
+// a stream that waits for the reset: at most max_workgroups persistent workgroups that take CTU after CTU in wavefront order and wait for
+// searched[picture][ctu] (the search plan's flags, uvgi_ctu_plan_done_flags) of each -- a CTU is filtered as soon as it is searched (the
+// order of encoder_state_worker_encode_lcu_search, src/encoderstate.c:808-853).  The search must have been LAUNCHED before this kernel
+// (a waiting workgroup holds its slot; the cap keeps the device for the search).
+int uvgi_filter_run(int bitdepth, int n_pictures, int pic_w, int pic_h, void *workspace, const int32_t *searched, int max_workgroups, void *stream);
+int uvgi_filter_reset(int n_pictures, int pic_w, int pic_h, void *workspace, void *stream);
+// ... the stage's own per-CTU "final" flags [picture][ctu] (DEVICE memory): 1 when the CTU's SAO decision and its part of the output picture
+// are published -- what uvgi_encode_slice_rows_behind waits for
+const int32_t *uvgi_filter_final_flags(int n_pictures, int pic_w, int pic_h, const void *workspace);
+
+// ---- ctu_search_pb.hip: P / B pictures IN FLIGHT behind their references, the filter stage inside the persistent search kernel -------
+// uvghip_ctu_search_pb with, per CTU, the in-loop filters right behind its search (what encoder_state_worker_encode_lcu_search does after
+// uvg_search_lcu, encoderstate.c:841-853), so that an output picture becomes final CTU by CTU and a per-CTU flag releases the CTUs of the
+// pictures behind.  ref_in_call[i * 16 + k]: the index (< i) of the picture of this call whose OUTPUT (filters[].out_*, pictures[].motion_out)
+// is reference k of picture i, or -1 for a reference complete before the call.  Requirements beyond uvghip_ctu_search_pb: params.qp ==
+// params.qp_c == frame_qp; a picture with a reference inside the call has inflight_margin = 11 (sao_type != 0) or 9.  Workspace:
+// uvghip_ctu_search_pb_workspace_bytes.  Everything is enqueued on `stream` in stream order; nothing waits for the device.
+// searched_flags (may be NULL): [n_pictures], non-NULL for a picture whose SEARCH runs in another launch beside this one (an I picture in
+// uvgi_ctu_plan_launch; slice_type 2, its filters only, CTU by CTU behind that launch's flags).  That launch must already be LAUNCHED and its
+// flags zeroed in stream order before this call's kernel; other_workgroups (0..512, and 0 when searched_flags is NULL) is its grid, which this
+// launch leaves the CUs for.
+int uvgi_search_pb_inflight(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, const uvgi_pb_filter *filters, const int32_t *ref_in_call,
+                            const int32_t *const *searched_flags, int other_workgroups, int n_pictures, void *workspace, void *stream);
+// where the in-flight launch raises a picture's per-CTU "final" flags (picture i at [i * ctus]): a consumer of the finished pictures that
+// runs beside the launch waits on them (uvghip_loop_plan_run_coder_behind).  The launch zeroes them in stream order before its kernel.
+const int32_t *uvgi_search_pb_inflight_final_flags(int n_pictures, int pic_w, int pic_h, const void *workspace);
+
+// ---- slice_coder.hip ------------------------------------------------------------------------------------------------------------------
+// The coder's picture table in `workspace` (uvghip_slice_rows_workspace_bytes): ordered == false uploads it synchronously (once, for a
+// table that later runs reuse: uvghip_encode_slice_rows with pictures == NULL); ordered == true in stream order on `st` (callers that take
+// a stream: nothing waits for it).
+int uvgi_slice_rows_prepare(const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, int n_pictures, void *workspace, bool ordered, hipStream_t st);
+// uvghip_encode_slice_rows with the table already prepared, for pictures whose search is complete but whose in-loop filters (the SAO
+// decisions the slice data carries) are finished by ANOTHER launch beside this one: a row waits for each of its CTUs' final_flags
+// ([picture][ctu]) and for the first CTU of the row above (its SAO models).  The caller orders the flags' zeroing before this call's
+// stream position.
+// ticket == NULL: one wave per row (I pictures in the flight, uvgi_search_pb_inflight_final_flags).
+// ticket != NULL: at most max_waves rows in progress -- persistent waves take row r of every picture, then row r + 1, from `ticket` (one
+// int32 of DEVICE memory the caller zeroes in stream order before the launch): behind a search that is still RUNNING a waiting row must not
+// hold what the search needs, and a wave per row of a whole clip does (uvghip_loop_plan_run_overlapped, uvgi_filter_final_flags).
+int uvgi_encode_slice_rows_behind(int bitdepth, const uvghip_ctu_params_t *params, int n_pictures, const int32_t *sao_info, const uint16_t *sao_models,
+                                  const int32_t *final_flags, int32_t *ticket, int max_waves, void *workspace, uint8_t *out, int row_cap,
+                                  int32_t *row_bytes, void *stream);
+
+// ---- the P / B slice descriptor the coder takes, from the picture's search descriptor (loop_pb.hip) -----------------------------------
+inline uvghip_slice_pb_t uvgi_slice_pb_of(const uvghip_ctu_pb_picture_t &s)
+{
+  uvghip_slice_pb_t d;
+  memset(&d, 0, sizeof d);
+  d.slice_type = s.slice_type; d.poc = s.poc; d.n_refs = s.n_refs;
+  for (int k = 0; k < 16; ++k) { d.ref_pocs[k] = s.ref_pocs[k]; d.l[0][k] = s.l[0][k]; d.l[1][k] = s.l[1][k]; }
+  d.l_size[0] = s.l_size[0]; d.l_size[1] = s.l_size[1];
+  d.tmvp = s.tmvp; d.max_merge = s.max_merge; d.merge_level = s.merge_level; d.frame_qp = s.frame_qp;
+  d.col = s.ref_motion[s.l[0][0]]; d.col_stride = s.ref_motion_stride;
+  d.inter4 = s.inter4; d.models_inter = s.models_inter;
+  return d;
+}

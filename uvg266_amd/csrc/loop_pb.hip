@@ -154,13 +154,7 @@ extern "C" int uvghip_loop_pb_run(int bitdepth, const uvghip_loop_pb_picture_t *
         UVGHIP_TRY(hipMemcpy2DAsync(q.out_v, (size_t)q.out_stride_c * b, p.rec_v, (size_t)p.rec_stride_c * b, (size_t)cw * b, ch, hipMemcpyDeviceToDevice, st));
       }
       cp[i - i0] = p;
-      uvghip_slice_pb_t &d = sl[i - i0];
-      d.slice_type = s.slice_type; d.poc = s.poc; d.n_refs = s.n_refs;
-      for (int k = 0; k < 16; ++k) { d.ref_pocs[k] = s.ref_pocs[k]; d.l[0][k] = s.l[0][k]; d.l[1][k] = s.l[1][k]; }
-      d.l_size[0] = s.l_size[0]; d.l_size[1] = s.l_size[1];
-      d.tmvp = s.tmvp; d.max_merge = s.max_merge; d.merge_level = s.merge_level; d.frame_qp = s.frame_qp;
-      d.col = s.ref_motion[s.l[0][0]]; d.col_stride = s.ref_motion_stride; d.reserved = 0;
-      d.inter4 = s.inter4; d.models_inter = s.models_inter;
+      sl[i - i0] = uvgi_slice_pb_of(s);
     }
     // the slice data of the run's pictures: the search's hand-over and the SAO decisions through the arithmetic coder (its tables are
     // uploaded in stream order: a later run's upload comes after the earlier run's coder on the stream)
@@ -172,7 +166,7 @@ extern "C" int uvghip_loop_pb_run(int bitdepth, const uvghip_loop_pb_picture_t *
   return 0;
 }
 
-// ---- pictures in flight behind their references: one call = one persistent launch for the whole DAG (uvghip_ctu_search_pb_inflight: the
+// ---- pictures in flight behind their references: one call = one persistent launch for the whole DAG (uvgi_search_pb_inflight: the
 // search with the per-CTU filters inside), then ONE coder launch over all pictures -- their QPs, lambdas and slice types may differ ----
 namespace {
 struct flight_t { size_t search, dbk, info, models, coder, row_bytes, rows, total; int row_cap; };
@@ -182,7 +176,7 @@ flight_t flight_of(int bitdepth, int n, int w, int h)
   flight_t L;
   size_t at = 0;
   auto take = [&](size_t bytes) { const size_t o = at; at = align_up(at + bytes, 256); return o; };
-  L.search = take(uvghip_ctu_search_pb_inflight_workspace_bytes(n, w, h));
+  L.search = take(uvghip_ctu_search_pb_workspace_bytes(n, w, h));
   L.dbk = take((size_t)n * ((size_t)w * h * 3 / 2) * b);
   L.info = take((size_t)n * ctus * 34 * 4);
   L.models = take((size_t)n * ctus * 6 * 2);
@@ -220,7 +214,7 @@ extern "C" const int32_t *uvghip_loop_pb_inflight_final_flags(int bitdepth, int 
 {
   if ((bitdepth != 8 && bitdepth != 10) || n_pictures <= 0 || pic_w <= 0 || pic_h <= 0 || !workspace) return nullptr;
   const flight_t L = flight_of(bitdepth, n_pictures, pic_w, pic_h);
-  return uvghip_ctu_search_pb_inflight_final_flags(n_pictures, pic_w, pic_h, static_cast<const unsigned char *>(workspace) + L.search);
+  return uvgi_search_pb_inflight_final_flags(n_pictures, pic_w, pic_h, static_cast<const unsigned char *>(workspace) + L.search);
 }
 
 extern "C" int uvghip_loop_pb_run_inflight(int bitdepth, const uvghip_loop_pb_picture_t *pictures, int n_pictures, int sao_type, const int32_t *ref_in_call, void *workspace,
@@ -248,7 +242,7 @@ extern "C" int uvghip_loop_pb_run_inflight_ext(int bitdepth, const uvghip_loop_p
   int32_t *sao_info = reinterpret_cast<int32_t *>(ws + L.info), *row_bytes = reinterpret_cast<int32_t *>(ws + L.row_bytes);
   uint16_t *sao_models = reinterpret_cast<uint16_t *>(ws + L.models);
   std::vector<uvghip_ctu_pb_picture_t> sp(n_pictures);
-  std::vector<uvghip_pb_filter_t> fl(n_pictures);
+  std::vector<uvgi_pb_filter> fl(n_pictures);
   std::vector<uvghip_ctu_picture_t> cp(n_pictures);
   std::vector<uvghip_slice_pb_t> sl(n_pictures);
   std::vector<const int32_t *> flags(n_pictures, nullptr);
@@ -259,7 +253,7 @@ extern "C" int uvghip_loop_pb_run_inflight_ext(int bitdepth, const uvghip_loop_p
     if (!q.out_y || !q.out_u || !q.out_v || q.out_stride < w || q.out_stride_c < w / 2) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run_inflight: output planes");
     if (ext && ext[i].searched_flags) flags[i] = ext[i].searched_flags; else coded.push_back(i);
     sp[i] = s;
-    uvghip_pb_filter_t &f = fl[i];
+    uvgi_pb_filter &f = fl[i];
     unsigned char *d = ws + L.dbk + (size_t)i * planes;
     f.dbk_y = d; f.dbk_u = d + plane; f.dbk_v = d + plane + plane / 4;
     f.dbk_stride = w; f.dbk_stride_c = w / 2;
@@ -268,18 +262,11 @@ extern "C" int uvghip_loop_pb_run_inflight_ext(int bitdepth, const uvghip_loop_p
     if (flags[i] && ext[i].sao_info && ext[i].sao_models) { f.sao_info = ext[i].sao_info; f.sao_models = ext[i].sao_models; }
     f.sao_type = sao_type; f.reserved = 0;
     cp[i] = s.pic;
-    uvghip_slice_pb_t &o = sl[i];
-    if (flags[i]) { memset(&o, 0, sizeof o); continue; }          // (not coded here)
-    o.slice_type = s.slice_type; o.poc = s.poc; o.n_refs = s.n_refs;
-    for (int k = 0; k < 16; ++k) { o.ref_pocs[k] = s.ref_pocs[k]; o.l[0][k] = s.l[0][k]; o.l[1][k] = s.l[1][k]; }
-    o.l_size[0] = s.l_size[0]; o.l_size[1] = s.l_size[1];
-    o.tmvp = s.tmvp; o.max_merge = s.max_merge; o.merge_level = s.merge_level; o.frame_qp = s.frame_qp;
-    o.col = s.ref_motion[s.l[0][0]]; o.col_stride = s.ref_motion_stride; o.reserved = 0;
-    o.inter4 = s.inter4; o.models_inter = s.models_inter;
+    if (!flags[i]) sl[i] = uvgi_slice_pb_of(s);          // (the others are not coded here)
   }
-  if (ext) {
-    if (int rc = uvghip_ctu_search_pb_inflight_ext(bitdepth, sp.data(), fl.data(), ref_in_call, flags.data(), other_workgroups, n_pictures, ws + L.search, stream)) return rc;
-  } else if (int rc = uvghip_ctu_search_pb_inflight(bitdepth, sp.data(), fl.data(), ref_in_call, n_pictures, ws + L.search, stream)) return rc;
+  if (int rc = uvgi_search_pb_inflight(bitdepth, sp.data(), fl.data(), ref_in_call, ext ? flags.data() : nullptr, ext ? other_workgroups : 0, n_pictures, ws + L.search,
+                                       stream))
+    return rc;
   // the slice data of every picture in one launch (a P / B picture's models start from its own frame_qp and slice type: `params` only names the size).
   // The coded pictures are a suffix of the call in practice (I pictures first); runs of them keep their place in the results' arrays.
   for (size_t a = 0; a < coded.size();) {

@@ -29,7 +29,7 @@ struct uvghip_loop_plan {
   int row_cap, hc;
   uint32_t *sums;                         // per picture: the three plane checksums of the hash SEI (filled on demand)
   uvghip_ctu_params_t ctu_params;
-  int fused;                              // the filters are ONE launch behind the search (uvghip_filter_pictures); `snap` holds the deblocked pictures
+  int fused;                              // the filters are ONE launch behind the search (uvgi_filter_run); `snap` holds the deblocked pictures
   void *filt_ws;
   int32_t *coder_ticket;                  // uvghip_loop_plan_run_overlapped: the persistent coder's row counter
   // uvghip_loop_plan_group_nals: the rows of the whole group gathered on the device and brought over in one copy (grown on demand)
@@ -68,7 +68,7 @@ layout_t layout_of(int bitdepth, int n, int w, int h)
   L.row_bytes = take((size_t)n * hc * 4);
   L.rows = take((size_t)n * hc * L.row_cap);
   L.sums = take((size_t)n * 3 * sizeof(uint32_t));
-  L.filt = take(uvghip_filter_pictures_workspace_bytes(n, w, h));
+  L.filt = take(uvgi_filter_workspace_bytes(n, w, h));
   L.tick = take(256);
   L.total = at;
   return L;
@@ -126,8 +126,8 @@ extern "C" int uvghip_loop_plan_create(int bitdepth, const uvghip_ctu_params_t *
   pl->row_cap = L.row_cap; pl->hc = hc;
   pl->sums = reinterpret_cast<uint32_t *>(ws + L.sums);
   pl->ctu_params = *params;
-  if (int rc = uvghip_slice_rows_prepare(params, sp.data(), n_pictures, pl->coder_ws)) { uvghip_ctu_plan_destroy(pl->search); delete pl; return rc; }
-  // The in-loop filters as ONE launch behind the search, a workgroup per CTU (uvghip_filter_pictures, ctu_filter.h) -- the default;
+  if (int rc = uvgi_slice_rows_prepare(params, sp.data(), n_pictures, pl->coder_ws, false, nullptr)) { uvghip_ctu_plan_destroy(pl->search); delete pl; return rc; }
+  // The in-loop filters as ONE launch behind the search, a workgroup per CTU (filters.hip, ctu_filter.h) -- the default;
   // UVGHIP_LOOP_UNFUSED=1 keeps the chain of whole-picture kernels (deblock snapshot, SAO statistics, decision, deblocking in place,
   // SAO apply: the same pictures and decisions, ~40 launches per picture).
   {
@@ -136,17 +136,17 @@ extern "C" int uvghip_loop_plan_create(int bitdepth, const uvghip_ctu_params_t *
     pl->filt_ws = ws + L.filt;
     pl->coder_ticket = reinterpret_cast<int32_t *>(ws + L.tick);
     if (pl->fused) {
-      std::vector<uvghip_pb_filter_t> fl(n_pictures);
+      std::vector<uvgi_pb_filter> fl(n_pictures);
       const size_t b = bitdepth == 8 ? 1 : 2, plane = (size_t)w * h * b;
       for (int i = 0; i < n_pictures; ++i) {
-        uvghip_pb_filter_t &f = fl[i];
+        uvgi_pb_filter &f = fl[i];
         unsigned char *d = pl->snap + (size_t)i * pl->snap_bytes;
         f.dbk_y = d; f.dbk_u = d + plane; f.dbk_v = d + plane + plane / 4; f.dbk_stride = w; f.dbk_stride_c = w / 2;
         f.out_y = pictures[i].out_y; f.out_u = pictures[i].out_u; f.out_v = pictures[i].out_v; f.out_stride = pictures[i].out_stride; f.out_stride_c = pictures[i].out_stride_c;
         f.sao_info = pl->sao_info + (size_t)i * pl->ctus * 34; f.sao_models = pl->sao_models + (size_t)i * pl->ctus * 6;
         f.sao_type = sao_type; f.reserved = 0;
       }
-      if (int rc = uvghip_filter_pictures_prepare(bitdepth, params, sp.data(), fl.data(), n_pictures, 2, pl->filt_ws)) { uvghip_ctu_plan_destroy(pl->search); delete pl; return rc; }
+      if (int rc = uvgi_filter_prepare(bitdepth, params, sp.data(), fl.data(), n_pictures, 2, pl->filt_ws)) { uvghip_ctu_plan_destroy(pl->search); delete pl; return rc; }
     }
   }
   // the CTU grids clipped to the picture: the rectangles sao_search_luma / _chroma hand to the decision (sao.c:605-668)
@@ -164,7 +164,6 @@ extern "C" int uvghip_loop_plan_create(int bitdepth, const uvghip_ctu_params_t *
   return 0;
 }
 
-extern "C" int uvghip_loop_plan_run_filters(uvghip_loop_plan_t *pl, void *stream);
 extern "C" int uvghip_loop_plan_run(uvghip_loop_plan_t *pl, void *stream)
 {
   UVGHIP_REQUIRE_READY();
@@ -173,9 +172,6 @@ extern "C" int uvghip_loop_plan_run(uvghip_loop_plan_t *pl, void *stream)
   return uvghip_loop_plan_run_filters(pl, stream);
 }
 
-extern "C" int uvghip_ctu_plan_reset(uvghip_ctu_plan_t *pl, void *stream);
-extern "C" int uvghip_ctu_plan_launch(uvghip_ctu_plan_t *pl, void *stream);
-extern "C" const int32_t *uvghip_ctu_plan_done_flags(const uvghip_ctu_plan_t *pl);
 extern "C" int uvghip_loop_plan_run_overlapped(uvghip_loop_plan_t *pl, void *stream)
 {
   UVGHIP_REQUIRE_READY();
@@ -202,20 +198,19 @@ extern "C" int uvghip_loop_plan_run_overlapped(uvghip_loop_plan_t *pl, void *str
     UVGHIP_TRY(hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming));
   }
   // all flags to zero in `stream`, the side streams behind that; then the search, so that it is in the queue before anything waits for it
-  if (int rc = uvghip_ctu_plan_reset(pl->search, stream)) return rc;
-  if (int rc = uvghip_filter_pictures_reset(pl->n, pl->w, pl->h, pl->filt_ws, stream)) return rc;
+  if (int rc = uvgi_ctu_plan_reset(pl->search, stream)) return rc;
+  if (int rc = uvgi_filter_reset(pl->n, pl->w, pl->h, pl->filt_ws, stream)) return rc;
   UVGHIP_TRY(hipMemsetAsync(pl->coder_ticket, 0, sizeof(int32_t), st));
   UVGHIP_TRY(hipEventRecord(pl->ev_fork, st));
-  if (int rc = uvghip_ctu_plan_launch(pl->search, stream)) return rc;
+  if (int rc = uvgi_ctu_plan_launch(pl->search, stream)) return rc;
   for (int i = 0; i < 2; ++i) UVGHIP_TRY(hipStreamWaitEvent(pl->side[i], pl->ev_fork, 0));
   // the filter stage: as many persistent workgroups as the pictures' wavefronts can have CTUs in progress, at most an eighth of the device
   const int wc = (pl->w + 63) / 64, per = wc < pl->hc ? wc : pl->hc;
   long long g = (long long)per * pl->n;
   if (g > filter_cap) g = filter_cap;
-  if (int rc = uvghip_filter_pictures_run_behind(pl->bitdepth, pl->n, pl->w, pl->h, pl->filt_ws, uvghip_ctu_plan_done_flags(pl->search), (int)g, pl->side[0])) return rc;
-  if (int rc = uvghip_encode_slice_rows_behind_capped(pl->bitdepth, &pl->ctu_params, nullptr, pl->n, pl->sao_info, pl->sao_models,
-                                                      uvghip_filter_pictures_final_flags(pl->n, pl->w, pl->h, pl->filt_ws), pl->coder_ticket, coder_cap, pl->coder_ws, pl->rows,
-                                                      pl->row_cap, pl->row_bytes, pl->side[1]))
+  if (int rc = uvgi_filter_run(pl->bitdepth, pl->n, pl->w, pl->h, pl->filt_ws, uvgi_ctu_plan_done_flags(pl->search), (int)g, pl->side[0])) return rc;
+  if (int rc = uvgi_encode_slice_rows_behind(pl->bitdepth, &pl->ctu_params, pl->n, pl->sao_info, pl->sao_models, uvgi_filter_final_flags(pl->n, pl->w, pl->h, pl->filt_ws),
+                                             pl->coder_ticket, coder_cap, pl->coder_ws, pl->rows, pl->row_cap, pl->row_bytes, pl->side[1]))
     return rc;
   for (int i = 0; i < 2; ++i) {
     UVGHIP_TRY(hipEventRecord(pl->ev_side[i], pl->side[i]));
@@ -239,7 +234,7 @@ extern "C" int uvghip_loop_plan_run_filters(uvghip_loop_plan_t *pl, void *stream
   const size_t b = pl->bitdepth == 8 ? 1 : 2;
   const int w = pl->w, h = pl->h, cw = w / 2, ch = h / 2;
   if (pl->fused) {        // one launch for the filters of every picture, one for the slice data
-    if (int rc = uvghip_filter_pictures_run(pl->bitdepth, pl->n, w, h, pl->filt_ws, stream)) return rc;
+    if (int rc = uvgi_filter_run(pl->bitdepth, pl->n, w, h, pl->filt_ws, nullptr, 0, stream)) return rc;
     return uvghip_encode_slice_rows(pl->bitdepth, &pl->ctu_params, nullptr, pl->n, pl->sao_info, pl->sao_models, pl->coder_ws, pl->rows, pl->row_cap, pl->row_bytes, stream);
   }
   for (int i = 0; i < pl->n; ++i) {
@@ -274,14 +269,10 @@ extern "C" int uvghip_loop_plan_run_filters(uvghip_loop_plan_t *pl, void *stream
 
 // ---- an all-intra plan whose pictures are filtered ELSEWHERE: the I pictures of a clip, searched here beside the in-flight P / B launch that
 // filters them CTU by CTU as they are searched (uvghip_loop_pb_run_inflight_ext) ----
-extern "C" int uvghip_ctu_plan_reset(uvghip_ctu_plan_t *pl, void *stream);
-extern "C" int uvghip_ctu_plan_launch(uvghip_ctu_plan_t *pl, void *stream);
-extern "C" int uvghip_ctu_plan_set_grid(uvghip_ctu_plan_t *pl, int max_workgroups);
-extern "C" const int32_t *uvghip_ctu_plan_done_flags(const uvghip_ctu_plan_t *pl);
-extern "C" int uvghip_loop_plan_search_reset(uvghip_loop_plan_t *pl, void *stream) { return pl ? uvghip_ctu_plan_reset(pl->search, stream) : uvghip_set_error(hipErrorInvalidValue, __func__); }
-extern "C" int uvghip_loop_plan_search_launch(uvghip_loop_plan_t *pl, void *stream) { return pl ? uvghip_ctu_plan_launch(pl->search, stream) : uvghip_set_error(hipErrorInvalidValue, __func__); }
-extern "C" int uvghip_loop_plan_set_search_grid(uvghip_loop_plan_t *pl, int max_workgroups) { return pl ? uvghip_ctu_plan_set_grid(pl->search, max_workgroups) : uvghip_set_error(hipErrorInvalidValue, __func__); }
-extern "C" const int32_t *uvghip_loop_plan_searched_flags(const uvghip_loop_plan_t *pl) { return pl ? uvghip_ctu_plan_done_flags(pl->search) : nullptr; }
+extern "C" int uvghip_loop_plan_search_reset(uvghip_loop_plan_t *pl, void *stream) { return pl ? uvgi_ctu_plan_reset(pl->search, stream) : uvghip_set_error(hipErrorInvalidValue, __func__); }
+extern "C" int uvghip_loop_plan_search_launch(uvghip_loop_plan_t *pl, void *stream) { return pl ? uvgi_ctu_plan_launch(pl->search, stream) : uvghip_set_error(hipErrorInvalidValue, __func__); }
+extern "C" int uvghip_loop_plan_set_search_grid(uvghip_loop_plan_t *pl, int max_workgroups) { return pl ? uvgi_ctu_plan_set_grid(pl->search, max_workgroups) : uvghip_set_error(hipErrorInvalidValue, __func__); }
+extern "C" const int32_t *uvghip_loop_plan_searched_flags(const uvghip_loop_plan_t *pl) { return pl ? uvgi_ctu_plan_done_flags(pl->search) : nullptr; }
 // the slice data alone (the pictures' SAO decisions are in the plan's arrays: uvghip_loop_plan_results)
 extern "C" int uvghip_loop_plan_run_coder(uvghip_loop_plan_t *pl, void *stream)
 {
@@ -295,8 +286,8 @@ extern "C" int uvghip_loop_plan_run_coder_behind(uvghip_loop_plan_t *pl, const i
 {
   UVGHIP_REQUIRE_READY();
   if (!pl || !final_flags) return uvghip_set_error(hipErrorInvalidValue, __func__);
-  return uvghip_encode_slice_rows_behind(pl->bitdepth, &pl->ctu_params, nullptr, pl->n, pl->sao_info, pl->sao_models, final_flags, pl->coder_ws, pl->rows, pl->row_cap,
-                                         pl->row_bytes, stream);
+  return uvgi_encode_slice_rows_behind(pl->bitdepth, &pl->ctu_params, pl->n, pl->sao_info, pl->sao_models, final_flags, nullptr, 0, pl->coder_ws, pl->rows,
+                                       pl->row_cap, pl->row_bytes, stream);
 }
 
 extern "C" int uvghip_loop_plan_slice_data(const uvghip_loop_plan_t *pl, const uint8_t **rows, const int32_t **row_bytes, int *row_cap, int *n_rows)

@@ -575,7 +575,7 @@ __device__ inline void alf_ctu(coder &c, row_state *R, const alf_dev &A, int k, 
 }
 
 // PERSIST: the launch is a capped number of waves that take row after row from a ticket counter -- row r of every picture, then row r + 1:
-// the order in which rows become codable behind a search that is still running (uvghip_encode_slice_rows_behind_capped) -- instead of a
+// the order in which rows become codable behind a search that is still running (uvgi_encode_slice_rows_behind) -- instead of a
 // wave per row: a waiting wave holds 10 KB of LDS a search workgroup cannot use.
 template <bool PERSIST = false>
 __global__ void __launch_bounds__(64)
@@ -892,8 +892,7 @@ extern "C" size_t uvghip_slice_rows_pb_workspace_bytes(int n_pictures)
   return n_pictures > 0 ? ((size_t)n_pictures * sizeof(pic_dev) + 255) / 256 * 256 + (size_t)n_pictures * sizeof(pb_dev) : 0;
 }
 
-// the picture table the kernel reads, uploaded once (synchronously); uvghip_encode_slice_rows with pictures == NULL reuses it
-extern "C" int uvghip_slice_rows_prepare(const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, int n_pictures, void *workspace)
+int uvgi_slice_rows_prepare(const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, int n_pictures, void *workspace, bool ordered, hipStream_t st)
 {
   UVGHIP_REQUIRE_READY();
   if (!params || !pictures || n_pictures <= 0 || !workspace) return uvghip_set_error(hipErrorInvalidValue, __func__);
@@ -901,24 +900,12 @@ extern "C" int uvghip_slice_rows_prepare(const uvghip_ctu_params_t *params, cons
   std::vector<pic_dev> pd(n_pictures);
   for (int i = 0; i < n_pictures; ++i) {
     if (!pictures[i].cu || !pictures[i].coeff || !pictures[i].models || pictures[i].cu_stride < wc * 16)
-      return uvghip_set_error(hipErrorInvalidValue, "uvghip_slice_rows_prepare: picture descriptor");
-    pd[i] = pic_dev{pictures[i].cu, pictures[i].coeff, pictures[i].models, pictures[i].cu_stride, 0};
-  }
-  UVGHIP_TRY(hipMemcpy(workspace, pd.data(), pd.size() * sizeof(pic_dev), hipMemcpyHostToDevice));
-  return 0;
-}
-
-// ... the same table in stream order (the callers that take a stream: nothing waits for it)
-static int prepare_ordered(const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, int n_pictures, void *workspace, hipStream_t st)
-{
-  const int wc = (params->pic_w + 63) / 64;
-  std::vector<pic_dev> pd(n_pictures);
-  for (int i = 0; i < n_pictures; ++i) {
-    if (!pictures[i].cu || !pictures[i].coeff || !pictures[i].models || pictures[i].cu_stride < wc * 16)
       return uvghip_set_error(hipErrorInvalidValue, "uvghip_encode_slice_rows: picture descriptor");
     pd[i] = pic_dev{pictures[i].cu, pictures[i].coeff, pictures[i].models, pictures[i].cu_stride, 0};
   }
-  return uvghip_upload_ordered(workspace, pd.data(), pd.size() * sizeof(pic_dev), st);
+  if (ordered) return uvghip_upload_ordered(workspace, pd.data(), pd.size() * sizeof(pic_dev), st);
+  UVGHIP_TRY(hipMemcpy(workspace, pd.data(), pd.size() * sizeof(pic_dev), hipMemcpyHostToDevice));
+  return 0;
 }
 
 extern "C" int uvghip_encode_slice_rows(int bitdepth, const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, int n_pictures,
@@ -931,55 +918,32 @@ extern "C" int uvghip_encode_slice_rows(int bitdepth, const uvghip_ctu_params_t 
     return uvghip_set_error(hipErrorInvalidValue, __func__);
   const int W = params->pic_w, H = params->pic_h, hc = (H + 63) / 64;
   if (W <= 0 || H <= 0 || (W & 7) || (H & 7) || params->qp < 0 || params->qp > 63) return uvghip_set_error(hipErrorInvalidValue, __func__);
-  if (pictures)
-    if (int rc = uvghip_slice_rows_prepare(params, pictures, n_pictures, workspace)) return rc;
   hipStream_t st = uvghip_stream(stream);
+  if (pictures)
+    if (int rc = uvgi_slice_rows_prepare(params, pictures, n_pictures, workspace, false, st)) return rc;
   slice_rows_kernel<false><<<n_pictures * hc, 64, 0, st>>>(static_cast<const pic_dev *>(workspace), nullptr, sao_info, sao_models, W, H, params->qp, bitdepth, out,
                                                     row_cap, row_bytes);
   UVGHIP_CHECK_LAUNCH();
 }
 
-// ... of pictures whose search is complete but whose in-loop filters (the SAO decisions the slice data carries) are being finished by ANOTHER
-// launch beside this one -- I pictures in the flight (uvghip_loop_pb_run_inflight_ext filters them CTU by CTU): final_flags are that
-// launch's per-CTU flags of these pictures ([picture][ctu], uvghip_loop_pb_inflight_final_flags), a row waits for each of its CTUs (and
-// for the first CTU of the row above: its SAO models).  The caller orders the flags' zeroing before this call's stream position.
-extern "C" int uvghip_encode_slice_rows_behind(int bitdepth, const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, int n_pictures,
-                                               const int32_t *sao_info, const uint16_t *sao_models, const int32_t *final_flags, void *workspace, uint8_t *out,
-                                               int row_cap, int32_t *row_bytes, void *stream)
+int uvgi_encode_slice_rows_behind(int bitdepth, const uvghip_ctu_params_t *params, int n_pictures, const int32_t *sao_info, const uint16_t *sao_models,
+                                  const int32_t *final_flags, int32_t *ticket, int max_waves, void *workspace, uint8_t *out, int row_cap,
+                                  int32_t *row_bytes, void *stream)
 {
   UVGHIP_REQUIRE_READY();
   UVGHIP_REQUIRE_DEPTH(bitdepth);
-  if (!params || n_pictures <= 0 || !workspace || !out || row_cap <= 0 || !row_bytes || !sao_info || !sao_models || !final_flags)
+  if (!params || n_pictures <= 0 || !workspace || !out || row_cap <= 0 || !row_bytes || !sao_info || !sao_models || !final_flags || (ticket && max_waves < 1))
     return uvghip_set_error(hipErrorInvalidValue, __func__);
   const int W = params->pic_w, H = params->pic_h, hc = (H + 63) / 64;
   if (W <= 0 || H <= 0 || (W & 7) || (H & 7) || params->qp < 0 || params->qp > 63) return uvghip_set_error(hipErrorInvalidValue, __func__);
   hipStream_t st = uvghip_stream(stream);
-  if (pictures)
-    if (int rc = prepare_ordered(params, pictures, n_pictures, workspace, st)) return rc;
-  slice_rows_kernel<false><<<n_pictures * hc, 64, 0, st>>>(static_cast<const pic_dev *>(workspace), nullptr, sao_info, sao_models, W, H, params->qp, bitdepth, out,
-                                                    row_cap, row_bytes, nullptr, final_flags);
-  UVGHIP_CHECK_LAUNCH();
-}
-
-// ... with at most max_waves rows in progress (persistent waves that take row r of every picture, then row r + 1, from `ticket`: one int32 of
-// DEVICE memory the caller zeroes in stream order before the launch): behind a search that is still RUNNING a waiting row must not hold what the
-// search needs -- a wave per row of a whole clip does (uvghip_loop_plan_run_overlapped).
-extern "C" int uvghip_encode_slice_rows_behind_capped(int bitdepth, const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, int n_pictures,
-                                                      const int32_t *sao_info, const uint16_t *sao_models, const int32_t *final_flags, int32_t *ticket, int max_waves,
-                                                      void *workspace, uint8_t *out, int row_cap, int32_t *row_bytes, void *stream)
-{
-  UVGHIP_REQUIRE_READY();
-  UVGHIP_REQUIRE_DEPTH(bitdepth);
-  if (!params || n_pictures <= 0 || !workspace || !out || row_cap <= 0 || !row_bytes || !sao_info || !sao_models || !final_flags || !ticket || max_waves < 1)
-    return uvghip_set_error(hipErrorInvalidValue, __func__);
-  const int W = params->pic_w, H = params->pic_h, hc = (H + 63) / 64;
-  if (W <= 0 || H <= 0 || (W & 7) || (H & 7) || params->qp < 0 || params->qp > 63) return uvghip_set_error(hipErrorInvalidValue, __func__);
-  hipStream_t st = uvghip_stream(stream);
-  if (pictures)
-    if (int rc = prepare_ordered(params, pictures, n_pictures, workspace, st)) return rc;
-  const int rows = n_pictures * hc, grid = rows < max_waves ? rows : max_waves;
-  slice_rows_kernel<true><<<grid, 64, 0, st>>>(static_cast<const pic_dev *>(workspace), nullptr, sao_info, sao_models, W, H, params->qp, bitdepth, out,
-                                               row_cap, row_bytes, nullptr, final_flags, ticket, n_pictures);
+  const int rows = n_pictures * hc;
+  if (ticket)
+    slice_rows_kernel<true><<<rows < max_waves ? rows : max_waves, 64, 0, st>>>(static_cast<const pic_dev *>(workspace), nullptr, sao_info, sao_models, W, H, params->qp,
+                                                                                bitdepth, out, row_cap, row_bytes, nullptr, final_flags, ticket, n_pictures);
+  else
+    slice_rows_kernel<false><<<rows, 64, 0, st>>>(static_cast<const pic_dev *>(workspace), nullptr, sao_info, sao_models, W, H, params->qp, bitdepth, out,
+                                                  row_cap, row_bytes, nullptr, final_flags);
   UVGHIP_CHECK_LAUNCH();
 }
 
@@ -994,7 +958,7 @@ extern "C" int uvghip_encode_slice_rows_alf(int bitdepth, const uvghip_ctu_param
   const int W = params->pic_w, H = params->pic_h, hc = (H + 63) / 64;
   if (W <= 0 || H <= 0 || (W & 7) || (H & 7) || params->qp < 0 || params->qp > 63) return uvghip_set_error(hipErrorInvalidValue, __func__);
   hipStream_t st = uvghip_stream(stream);
-  if (int rc = prepare_ordered(params, pictures, n_pictures, workspace, st)) return rc;
+  if (int rc = uvgi_slice_rows_prepare(params, pictures, n_pictures, workspace, true, st)) return rc;
   std::vector<alf_dev> ad(n_pictures);
   for (int i = 0; i < n_pictures; ++i) {
     const uvghip_slice_alf_t &q = alf[i];
@@ -1024,7 +988,7 @@ extern "C" int uvghip_encode_slice_rows_pb(int bitdepth, const uvghip_ctu_params
   const int W = params->pic_w, H = params->pic_h, hc = (H + 63) / 64;
   if (W <= 0 || H <= 0 || (W & 7) || (H & 7) || params->qp < 0 || params->qp > 63) return uvghip_set_error(hipErrorInvalidValue, __func__);
   hipStream_t st = uvghip_stream(stream);
-  if (int rc = prepare_ordered(params, pictures, n_pictures, workspace, st)) return rc;
+  if (int rc = uvgi_slice_rows_prepare(params, pictures, n_pictures, workspace, true, st)) return rc;
   std::vector<pb_dev> pd(n_pictures);
   for (int i = 0; i < n_pictures; ++i) {
     const uvghip_slice_pb_t &q = pb[i];

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/uvg266_hip.h"
+#include "internal.h"          // the steps the library's files call in each other, outside the C ABI
 
 #define UVGHIP_WAVE 64
 

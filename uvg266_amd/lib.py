@@ -258,7 +258,6 @@ SIGNATURES = {
     "uvghip_ctu_plan_run": (c_int, [c_vp, c_vp]),
     "uvghip_ctu_plan_destroy": (None, [c_vp]),
     "uvghip_slice_rows_workspace_bytes": (ctypes.c_size_t, [c_int]),
-    "uvghip_slice_rows_prepare": (c_int, [c_vp, c_vp, c_int, c_vp]),
     "uvghip_loop_plan_slice_data": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
     "uvghip_encode_slice_rows": (c_int, [c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
     "uvghip_loop_plan_picture_nals": (c_int, [c_vp, c_int, c_int, c_vp, ctypes.c_size_t, c_vp, c_vp]),
@@ -299,26 +298,14 @@ SIGNATURES = {
     "uvghip_loop_pb_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
     "uvghip_loop_pb_run": (c_int, [c_int, c_vp, c_int, c_int, c_vp, c_vp]),
     "uvghip_loop_pb_results": (c_int, [c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
-    "uvghip_filter_pictures_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
-    "uvghip_filter_pictures_prepare": (c_int, [c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
-    "uvghip_filter_pictures_run": (c_int, [c_int, c_int, c_int, c_int, c_vp, c_vp]),
-    "uvghip_ctu_search_pb_inflight_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
-    "uvghip_ctu_search_pb_inflight": (c_int, [c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
     "uvghip_loop_pb_run_inflight_ext": (c_int, [c_int, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp]),
-    "uvghip_ctu_search_pb_inflight_ext": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
     "uvghip_loop_plan_search_reset": (c_int, [c_vp, c_vp]),
     "uvghip_loop_plan_search_launch": (c_int, [c_vp, c_vp]),
     "uvghip_loop_plan_set_search_grid": (c_int, [c_vp, c_int]),
     "uvghip_loop_plan_searched_flags": (c_vp, [c_vp]),
     "uvghip_loop_plan_run_coder": (c_int, [c_vp, c_vp]),
     "uvghip_loop_plan_run_coder_behind": (c_int, [c_vp, c_vp, c_vp]),
-    "uvghip_encode_slice_rows_behind": (c_int, [c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
     "uvghip_loop_pb_inflight_final_flags": (c_vp, [c_int, c_int, c_int, c_int, c_vp]),
-    "uvghip_ctu_search_pb_inflight_final_flags": (c_vp, [c_int, c_int, c_int, c_vp]),
-    "uvghip_ctu_plan_reset": (c_int, [c_vp, c_vp]),
-    "uvghip_ctu_plan_launch": (c_int, [c_vp, c_vp]),
-    "uvghip_ctu_plan_set_grid": (c_int, [c_vp, c_int]),
-    "uvghip_ctu_plan_done_flags": (c_vp, [c_vp]),
     "uvghip_loop_pb_inflight_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
     "uvghip_loop_pb_run_inflight": (c_int, [c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp]),
     "uvghip_loop_pb_inflight_results": (c_int, [c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
@@ -330,10 +317,6 @@ SIGNATURES = {
     "uvghip_loop_plan_create": (c_int, [c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
     "uvghip_loop_plan_run": (c_int, [c_vp, c_vp]),
     "uvghip_loop_plan_run_overlapped": (c_int, [c_vp, c_vp]),
-    "uvghip_encode_slice_rows_behind_capped": (c_int, [c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp]),
-    "uvghip_filter_pictures_reset": (c_int, [c_int, c_int, c_int, c_vp, c_vp]),
-    "uvghip_filter_pictures_run_behind": (c_int, [c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp]),
-    "uvghip_filter_pictures_final_flags": (c_vp, [c_int, c_int, c_int, c_vp]),
     "uvghip_loop_plan_run_search": (c_int, [c_vp, c_vp]),
     "uvghip_loop_plan_run_filters": (c_int, [c_vp, c_vp]),
     "uvghip_loop_plan_results": (c_int, [c_vp, c_vp, c_vp]),
