@@ -799,6 +799,15 @@ def sweep_cases(n, seed, widths=(64, 72, 128, 136, 192, 200, 256, 264, 320), hei
              rng.choice([0, 3, 10, 17, 22, 27, 32, 37, 45, 51]), rng.randrange(0, 64) + 1000 * rng.choice([0, 1, 2, 3, 4])) for _ in range(n)]
 
 
+def small_sweep_cases(n, seed, sides=(8, 16, 24, 40, 56, 72)):
+    """n (W, H, depth, qp, t) combinations of pictures of at most one CTU and a partial one per side (a single CTU column or row: the
+    wavefront of one CTU), both depths, QP 0..51, every picture kind.  sweep_cases' grid and seeds stay as they are."""
+    import random
+    rng = random.Random(seed)
+    return [(rng.choice(list(sides)), rng.choice(list(sides)), rng.choice([8, 10]), rng.randrange(0, 52),
+             rng.randrange(0, 64) + 1000 * rng.choice([0, 1, 2, 3, 4])) for _ in range(n)]
+
+
 # ---- the picture's NAL units behind the parameter sets (checker for uvghip_write_picture_nals / uvghip_picture_checksum) ----
 def picture_checksum(plane, depth):
     """uvg_image_checksum of one plane (src/strategies/generic/nal-generic.c:68-92): sum of (byte ^ mask) over the samples' bytes."""
@@ -878,6 +887,7 @@ def inter_reconstruct(g, B):
     W, Hh, depth, qp0, frames = (int(a) for a in g["dims"])
     top = (1 << depth) - 1
     final = [B.picture((g["final_y"][f], g["final_u"][f], g["final_v"][f])) for f in range(frames)]
+    coded = {int(r[51]): int(m[0]) for m, r in zip(g["meta"], g["refs"])}      # POC -> coded picture (the golden's arrays are in coding order)
     seen = dict(inter=0, bi=0, frac=0, resid=0, outside=0)
 
     def predict_list(ref, x, y, n, mv, want_hi):
@@ -922,7 +932,7 @@ def inter_reconstruct(g, B):
             preds = []
             for l in used:
                 poc = int(pocs[int(lists[l][ridx[l]])])
-                preds.append(predict_list(final[poc], x, y, n, mvs[l], len(used) == 2))
+                preds.append(predict_list(final[coded[poc]], x, y, n, mvs[l], len(used) == 2))
                 seen["frac"] += (mvs[l][0] & 15) != 0
                 seen["outside"] += x + (mvs[l][0] >> 4) < 0 or y + (mvs[l][1] >> 4) < 0 or x + (mvs[l][0] >> 4) + n > W
             if len(used) == 2:
@@ -1053,7 +1063,34 @@ def rising_picture(W, H, t, depth):
     return tuple(out)
 
 
-CLIP_GENERATORS = {0: None, 1: "clip_picture", 2: "plateau_picture", 3: "rising_picture"}          # the `clip` key of a ref_inter_* golden
+_NOISE_BASE = {}
+
+
+def noise_clip_picture(W, H, t, depth):
+    """Picture t of an arbitrarily long clip at the content extremes: a window into a full-range white-noise base at twice the resolution,
+    2x2-averaged, moving by whole and half samples per picture (forth and back like clip_picture), plus a small noise term of its own
+    (+-2 at 8 bit), with two hard-edged plateaus at exactly 0 and at the largest sample value -- prediction plus residual clips there."""
+    key = (W, H, depth)
+    if key not in _NOISE_BASE:
+        _NOISE_BASE.clear()
+        _NOISE_BASE[key] = varied_picture(2 * (W + 48), 2 * (H + 48), 3013, depth)        # (the window reaches 2 * 38 rows down at t % 24 = 12)
+    m = 12 - abs(t % 24 - 12)
+    rng = np.random.default_rng(5000 + t)
+    top = (1 << depth) - 1
+    out = []
+    for b, c in zip(_NOISE_BASE[key], (0, 1, 1)):
+        w, h = W >> c, H >> c
+        sx, sy = (16 + 3 * m) >> c, (16 + 5 * m) >> c
+        a = b[sy:sy + 2 * h, sx:sx + 2 * w].astype(np.int64)
+        p = (a.reshape(h, 2, w, 2).sum(axis=(1, 3)) + 2) >> 2
+        p = p + rng.integers(-2, 3, p.shape) * (1 << (depth - 8))
+        p[h // 4:h // 2, w // 8:3 * w // 8] = 0
+        p[h // 2:3 * h // 4, 5 * w // 8:7 * w // 8] = top
+        out.append(np.clip(p, 0, top).astype(b.dtype))
+    return tuple(out)
+
+
+CLIP_GENERATORS = {0: None, 1: "clip_picture", 2: "plateau_picture", 3: "rising_picture", 4: "noise_clip_picture"}          # the `clip` key of a ref_inter_* golden
 
 
 # ---- P / B pictures: the inter search of the oracle (oracle/orc_search.c + orc_search_inter.inc) ---------------------------------

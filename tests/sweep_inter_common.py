@@ -7,16 +7,24 @@ import helpers as H
 
 def sequence(kind, W, Hh, depth, frames, seed):
     """Synthetic sequences: 'pan' a noisy picture moving by whole and fractional samples, 'fast' large motion (vectors leave the picture),
-    'noise' independent noise on a still (little inter gain: intra CUs inside B pictures), 'still' identical pictures (everything skipped)."""
+    'noise' independent noise on a still (little inter gain: intra CUs inside B pictures), 'still' identical pictures (everything skipped),
+    'white' full-range white noise moving by whole samples plus +-4 (8 bit) of its own, 'saturated' the pan at four times the contrast:
+    plateaus at exactly 0 and at the largest value with hard edges, where prediction plus residual clips."""
     rng = np.random.default_rng(seed)
     mx = (1 << depth) - 1
     big = H.varied_picture(4 * (W + 160), 4 * (Hh + 160), 2100 + seed, depth)
+    white = H.varied_picture(W + 64, Hh + 64, 3100 + seed, depth) if kind == "white" else None
     out = []
     for t in range(frames):
         pic = []
-        for b, c in zip(big, (0, 1, 1)):
+        for i, (b, c) in enumerate(zip(big, (0, 1, 1))):
             w, h = W >> c, Hh >> c
-            if kind == "pan":
+            if kind == "white":
+                sx, sy = (8 + 5 * t) >> c, (8 + 3 * t) >> c
+                p = white[i].astype(np.int64)[sy:sy + h, sx:sx + w] + rng.integers(-4, 5, (h, w)) * (1 << (depth - 8))
+                pic.append(np.clip(p, 0, mx).astype(b.dtype))
+                continue
+            if kind in ("pan", "saturated"):
                 sx, sy = (80 + 7 * t) >> c, (120 + 5 * t) >> c
             elif kind == "fast":
                 sx, sy = ((40 + 150 * t) % 640) >> c, ((400 - 90 * t) % 640) >> c
@@ -26,6 +34,8 @@ def sequence(kind, W, Hh, depth, frames, seed):
             p = (a.reshape(h, 4, w, 4).sum(axis=(1, 3)) + 8) >> 4
             if kind == "noise":
                 p = p + rng.integers(-24, 25, p.shape) * (1 << (depth - 8))
+            if kind == "saturated":
+                p = (p - (1 << (depth - 1))) * 4 + (1 << (depth - 1))
             pic.append(np.clip(p, 0, mx).astype(b.dtype))
         out.append(tuple(pic))
     return out
@@ -42,6 +52,15 @@ CASES = [  # kind, W, H, golden the frame states come from, tools (tmvp, max_mer
     ("pan", 72, 72, "ref_inter_192x128_8_qp17_5frames", (0, 5, 2, 1, 4, 1)),
     ("fast", 192, 64, "ref_inter_264x136_8_qp32_9frames", (1, 6, 2, 1, 4, 0)),
     ("noise", 64, 72, "ref_inter_136x72_10_qp22_4frames", (1, 6, 2, 1, 4, 1)),
+    # the QP and content extremes (frame QPs 0 / 4 / 5 and 50 / 51; 10 bit at QP 0..5 and 46..51) and pictures smaller than one CTU
+    ("white", 136, 72, "ref_inter_136x72_8_qp0_5frames_noise", (1, 6, 2, 1, 4, 1)),
+    ("saturated", 136, 72, "ref_inter_136x72_8_qp51_5frames_clip", (1, 6, 2, 1, 4, 1)),
+    ("white", 40, 24, "ref_inter_136x72_8_qp51_5frames_clip", (1, 6, 2, 1, 4, 1)),
+    ("saturated", 8, 64, "ref_inter_136x72_8_qp0_5frames_noise", (1, 6, 2, 1, 4, 1)),
+    ("white", 72, 64, "ref_inter_136x72_10_qp0_4frames_noise", (1, 6, 2, 1, 4, 1)),
+    ("saturated", 64, 72, "ref_inter_136x72_10_qp48_9frames_ra8", (1, 6, 2, 1, 4, 1)),
+    ("fast", 40, 24, "ref_inter_40x24_8_qp27_5frames_clip", (1, 6, 2, 1, 4, 1)),
+    ("pan", 24, 40, "ref_inter_136x72_8_qp0_5frames_noise", (0, 5, 2, 0, 4, 0)),
 ]
 
 

@@ -6,7 +6,8 @@ import pytest
 import helpers as H
 
 
-@pytest.mark.parametrize("name", ["ref_ctu_832x480_8_qp22", "ref_ctu_416x240_10_qp37", "ref_ctu_320x192_8_qp42", "ref_ctu_192x128_10_qp12", "ref_ctu_256x128_8_qp7", "ref_ctu_264x136_10_qp32"])
+@pytest.mark.parametrize("name", ["ref_ctu_832x480_8_qp22", "ref_ctu_416x240_10_qp37", "ref_ctu_320x192_8_qp42", "ref_ctu_192x128_10_qp12", "ref_ctu_256x128_8_qp7", "ref_ctu_264x136_10_qp32",
+                                  "ref_ctu_136x72_10_qp0", "ref_ctu_200x136_8_qp51", "ref_ctu_40x24_8_qp22", "ref_ctu_24x136_10_qp37"])
 def test_emulated_kernel_equals_the_reference_run(name):
     g = H.ctu_golden(name)
     W, Hh, depth, qp, y, u, v = H.golden_source(g)
@@ -39,6 +40,20 @@ def test_outcome_does_not_depend_on_when_a_cu_cost_arrives():
     W, Hh, depth, qp, y, u, v = H.golden_source(g)
     r = H.emul_search_picture(depth, H.search_params(W, Hh, qp), y, u, v, lazy=True)
     assert np.array_equal(r["models"], g["models"]) and np.array_equal(r["rec_y"], g["rec_y"])
+
+
+def test_sweep_of_tiny_pictures_equals_the_oracle():
+    """48 pictures with sides of 8..72 (one CTU or less across, partial CTUs only, a wavefront of one CTU column or row), both depths,
+    QP 0..51, every kind of content: the kernel's source on the host against the oracle (tools/refcheck/sweep_ctu.py tiny holds the
+    oracle to the real encoder on the same grid)."""
+    orc = H.load_oracle()
+    for W, Hh, depth, qp, t in H.small_sweep_cases(48, 8):
+        prm = H.search_params(W, Hh, qp)
+        pic = H.varied_picture(W, Hh, t, depth)
+        r = H.emul_search_picture(depth, prm, *pic)
+        o = H.oracle_search_picture(orc, depth, prm, *pic)
+        assert np.array_equal(H.ctu_crcs(r, W, Hh), H.ctu_crcs(o, W, Hh)), (W, Hh, depth, qp, t)
+        assert np.array_equal(r["models"], o["models"]), (W, Hh, depth, qp, t)
 
 
 @pytest.mark.parametrize("dmin,dmax,combine", [(1, 3, 1), (1, 2, 1), (1, 1, 1), (2, 4, 0), (2, 2, 0), (3, 4, 0)])

@@ -27,7 +27,8 @@ def run_gpu(hip, depth, prm, pictures):
     return out
 
 
-@pytest.mark.parametrize("name", ["ref_ctu_832x480_8_qp22", "ref_ctu_416x240_10_qp37", "ref_ctu_320x192_8_qp42", "ref_ctu_192x128_10_qp12", "ref_ctu_256x128_8_qp7", "ref_ctu_264x136_10_qp32"])
+@pytest.mark.parametrize("name", ["ref_ctu_832x480_8_qp22", "ref_ctu_416x240_10_qp37", "ref_ctu_320x192_8_qp42", "ref_ctu_192x128_10_qp12", "ref_ctu_256x128_8_qp7", "ref_ctu_264x136_10_qp32",
+                                  "ref_ctu_136x72_10_qp0", "ref_ctu_200x136_8_qp51", "ref_ctu_40x24_8_qp22", "ref_ctu_24x136_10_qp37"])
 def test_every_ctu_equals_the_reference_run(hip, name):
     g = H.ctu_golden(name)
     W, Hh, depth, qp, y, u, v = H.golden_source(g)
@@ -97,6 +98,18 @@ def test_sweep_of_small_pictures_equals_the_oracle(hip, orc):
     (smooth, noisy, white noise, lone impulses): the device search against the oracle, which tools/refcheck/sweep_ctu.py holds to the
     real encoder on the same grid (1000 combinations at the time of writing)."""
     for W, Hh, depth, qp, t in H.sweep_cases(48, 2024):
+        prm = H.search_params(W, Hh, qp)
+        pic = H.varied_picture(W, Hh, t, depth)
+        r = run_gpu(hip, depth, prm, [pic])[0]
+        o = H.oracle_search_picture(orc, depth, prm, *pic)
+        assert np.array_equal(H.ctu_crcs(r, W, Hh), H.ctu_crcs(o, W, Hh)), (W, Hh, depth, qp, t)
+        assert np.array_equal(r["models"], o["models"]), (W, Hh, depth, qp, t)
+
+
+def test_sweep_of_tiny_pictures_equals_the_oracle(hip, orc):
+    """48 pictures with sides of 8..72 (partial CTUs only, a wavefront of one CTU column or row), both depths, QP 0..51, every kind of
+    content: the device search against the oracle (held to the real encoder on this grid by tools/refcheck/sweep_ctu.py tiny)."""
+    for W, Hh, depth, qp, t in H.small_sweep_cases(48, 72):
         prm = H.search_params(W, Hh, qp)
         pic = H.varied_picture(W, Hh, t, depth)
         r = run_gpu(hip, depth, prm, [pic])[0]

@@ -12,7 +12,9 @@ pytestmark = pytest.mark.gpu
 GOLDENS = ["ref_inter_136x72_10_qp22_4frames", "ref_inter_192x128_8_qp17_5frames", "ref_inter_264x136_8_qp32_9frames",
            # other tools than --preset medium's: P slices (no bi-prediction) without the temporal candidate; no fractional search, no early skip
            "ref_inter_136x72_8_qp27_4frames_p_notmvp", "ref_inter_192x128_10_qp24_4frames_subme0_noskip",
-           "ref_inter_136x72_8_qp27_17frames_ra16", "ref_inter_136x72_10_qp22_17frames_ra16", "ref_inter_136x72_8_qp27_9frames_ra8", "ref_inter_136x200_8_qp27_11frames_owf1", "ref_inter_136x72_8_qp27_5frames_rd1", "ref_inter_136x72_8_qp27_33frames_ra16p16"]
+           "ref_inter_136x72_8_qp27_17frames_ra16", "ref_inter_136x72_10_qp22_17frames_ra16", "ref_inter_136x72_8_qp27_9frames_ra8", "ref_inter_136x200_8_qp27_11frames_owf1", "ref_inter_136x72_8_qp27_5frames_rd1", "ref_inter_136x72_8_qp27_33frames_ra16p16",
+           # the QP and content extremes, a picture smaller than one CTU
+           "ref_inter_136x72_8_qp0_5frames_noise", "ref_inter_136x72_10_qp0_4frames_noise", "ref_inter_136x72_8_qp51_5frames_clip", "ref_inter_136x72_10_qp48_9frames_ra8", "ref_inter_40x24_8_qp27_5frames_clip"]
 
 
 def device_pictures(W, Hh, depth, pics, P, repeat=1):
@@ -108,8 +110,8 @@ def test_every_wave_count_of_the_kernel_gives_the_same_pictures(hip, waves, monk
             assert H.compare_device_inter_picture(W, Hh, d, result_of(W, Hh, t)) == [], (name, f"frame {fr}")
 
 
-@pytest.mark.parametrize("name", GOLDENS)
-def test_device_search_then_device_coder_gives_the_encoders_slice_data(hip, name):
+@pytest.mark.parametrize("name", [n for n in GOLDENS if n != "ref_inter_136x72_8_qp51_5frames_clip"])     # (41 bytes of P / B slice data at QP 51:
+def test_device_search_then_device_coder_gives_the_encoders_slice_data(hip, name):                       # below the test's own floor)
     """Both halves on the device, nothing of the encoder's in between: uvghip_ctu_search_pb's hand-over (side information, second table,
     levels, models) goes straight into uvghip_encode_slice_rows_pb; with the encoder's SAO decisions the rows are the slice data of
     every P / B picture inside the encoder's .266, byte for byte."""

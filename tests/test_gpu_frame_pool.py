@@ -134,3 +134,46 @@ def test_tiled_pictures_through_the_pool_equal_the_tiles_plans(hip, depth, w, h,
         for a, b in zip((y, u, v), want[i][0]):
             assert np.array_equal(a, b), f"picture {i}"
         assert rows == want[i][1], f"picture {i}: substreams"
+
+
+@pytest.mark.parametrize("depth", [8, 10])
+def test_full_range_noise_at_qp0_through_the_pool(hip, depth):
+    """Full-range white noise at QP 0 codes to more bytes than the raw picture (1.6 x at 8 bit: 23.9 kB of slice data for a 136x72 picture
+    of 14.7 kB): the pool's pictures and rows still equal the loop plans', with and without tiles, and the slots stay usable."""
+    import torch
+    from uvg266_amd import api
+    w, h, grid = 136, 72, ([2, 1], [1, 1])
+    P = api.ctu_params(w, h, 0)
+    pics = [H.varied_picture(w, h, 3000 + s, depth) for s in range(3)]
+
+    want = [loop_plan_result(P, yuv) for yuv in pics]
+    pool = api.FramePool(P, depth, n_slots=2, group_max=2)
+    pool.begin(0, P, pics[0])
+    pool.begin(1, P, pics[1])
+    got = [pool.finish(0)]
+    pool.begin(0, P, pics[2])
+    got += [pool.finish(1), pool.finish(0)]
+    for i, ((y, u, v), rows) in enumerate(got):
+        for a, b in zip((y, u, v), want[i][0]):
+            assert np.array_equal(a, b), f"picture {i}"
+        assert rows == want[i][1], f"picture {i}: rows"
+
+    want = []
+    for yuv in pics:
+        tl = api.TiledLoop(P, [tuple(torch.from_numpy(np.ascontiguousarray(p)).cuda() for p in yuv)], grid)
+        tl.run()
+        lens, data, _ = tl.substreams()
+        at = np.concatenate([[0], np.cumsum(lens[0])])
+        torch.cuda.synchronize()
+        want.append((tuple(t.cpu().numpy() for t in tl.out[0]),
+                     [data[at[r]:at[r + 1]].tobytes() for r in range(lens.shape[1])]))
+    pool = api.FramePool(P, depth, n_slots=2, group_max=2, tiles=grid)
+    pool.begin(0, P, pics[0])
+    pool.begin(1, P, pics[1])
+    got = [pool.finish(0)]
+    pool.begin(0, P, pics[2])
+    got += [pool.finish(1), pool.finish(0)]
+    for i, ((y, u, v), rows) in enumerate(got):
+        for a, b in zip((y, u, v), want[i][0]):
+            assert np.array_equal(a, b), f"tiled picture {i}"
+        assert rows == want[i][1], f"tiled picture {i}: substreams"

@@ -38,7 +38,9 @@ class DeviceBlocks:
         return r[0].cpu().numpy().astype(np.int32)
 
 
-@pytest.mark.parametrize("name", ["ref_inter_192x128_8_qp17_5frames", "ref_inter_136x72_10_qp22_4frames"])
+@pytest.mark.parametrize("name", ["ref_inter_192x128_8_qp17_5frames", "ref_inter_136x72_10_qp22_4frames",
+                                  "ref_inter_136x72_8_qp0_5frames_noise", "ref_inter_136x72_10_qp0_4frames_noise",
+                                  "ref_inter_136x72_10_qp22_17frames_ra16"])          # random access: references found by POC, arrays in coding order
 def test_device_kernels_reconstruct_the_encoders_inter_pictures(hip, name):
     g = H.ctu_golden(name)
     seen = H.inter_reconstruct(g, DeviceBlocks(int(g["dims"][2])))

@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("name", ["ref_ctu_832x480_8_qp22", "ref_ctu_416x240_10_qp37", "ref_ctu_320x192_8_qp42", "ref_ctu_192x128_10_qp12", "ref_ctu_256x128_8_qp7", "ref_ctu_264x136_10_qp32",
                                   "ref_ctucrc_1920x1080_8_qp22", "ref_ctucrc_1920x1080_10_qp27",
-                                  "ref_ctucrc_3840x2160_10_qp22"])
+                                  "ref_ctucrc_3840x2160_10_qp22", "ref_ctu_136x72_10_qp0", "ref_ctu_200x136_8_qp51", "ref_ctu_40x24_8_qp22", "ref_ctu_24x136_10_qp37"])
 def test_slice_data_equals_the_encoders(hip, name):
     import torch
     from uvg266_amd import api
@@ -91,7 +91,33 @@ def test_sweep_whole_loop_equals_the_oracle_chain(hip, orc):
         assert np.array_equal(np.concatenate([[0], np.cumsum(nb)]), off) and np.array_equal(got, want), case
 
 
-@pytest.mark.parametrize("name", ["ref_ctu_832x480_8_qp22", "ref_ctu_416x240_10_qp37", "ref_ctu_264x136_10_qp32", "ref_ctucrc_1920x1080_8_qp22", "ref_ctucrc_3840x2160_10_qp22"])
+def test_sweep_of_tiny_pictures_whole_loop_equals_the_oracle_chain(hip, orc):
+    """The same whole loop on 32 pictures with sides of 8..72 (partial CTUs only, a wavefront of one CTU column or row), both depths,
+    QP 0..51, every kind of content (helpers.small_sweep_cases)."""
+    import torch
+    from uvg266_amd import api
+    for W, Hh, depth, qp, t in H.small_sweep_cases(32, 4242):
+        prm = H.search_params(W, Hh, qp)
+        y, u, v = H.varied_picture(W, Hh, t, depth)
+        cl = api.ClosedLoop(api.ctu_params(W, Hh, qp, lam=prm.lam), [tuple(torch.from_numpy(np.ascontiguousarray(p)).cuda() for p in (y, u, v))])
+        cl.run()
+        out, nbytes = cl.slice_data()
+        info, models = cl.results()
+        nb = nbytes.cpu().numpy()[0]
+        got = np.concatenate([out[0, r, :nb[r]].cpu().numpy() for r in range(len(nb))])
+        final = [p.cpu().numpy() for p in cl.out[0]]
+        s = H.oracle_search_picture(orc, depth, prm, y, u, v)
+        f = H.oracle_sao_picture(orc, depth, W, Hh, qp, prm.lam, (y, u, v), (s["rec_y"], s["rec_u"], s["rec_v"]), H.scu_from_cu(s["cu"], qp))
+        want, off, _ = H.oracle_encode_rows(orc, depth, prm, s, f["sao"])
+        case = (W, Hh, depth, qp, t)
+        assert np.array_equal(H.sao_info_comparable(info[0]), H.sao_info_comparable(f["sao"])), case
+        for a, k in zip(final, ("final_y", "final_u", "final_v")):
+            assert np.array_equal(a, f[k]), (case, k)
+        assert np.array_equal(np.concatenate([[0], np.cumsum(nb)]), off) and np.array_equal(got, want), case
+
+
+@pytest.mark.parametrize("name", ["ref_ctu_832x480_8_qp22", "ref_ctu_416x240_10_qp37", "ref_ctu_264x136_10_qp32", "ref_ctucrc_1920x1080_8_qp22", "ref_ctucrc_3840x2160_10_qp22",
+                                  "ref_ctu_136x72_10_qp0", "ref_ctu_200x136_8_qp51", "ref_ctu_40x24_8_qp22", "ref_ctu_24x136_10_qp37"])
 def test_overlapped_run_equals_the_encoders(hip, name):
     """uvghip_loop_plan_run_overlapped: the filter stage BESIDE the search (persistent workgroups behind its per-CTU flags), the coder behind the
     filter stage's flags -- the same slice data, SAO decisions and output pictures as the three launches one after the other, several

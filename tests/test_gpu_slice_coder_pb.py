@@ -21,7 +21,8 @@ def models_u32(m, n):
     return np.ascontiguousarray(s0 | (s1 << 16))
 
 
-@pytest.mark.parametrize("name", ["ref_inter_192x128_8_qp17_5frames", "ref_inter_136x72_10_qp22_4frames", "ref_inter_264x136_8_qp32_9frames"])
+@pytest.mark.parametrize("name", ["ref_inter_192x128_8_qp17_5frames", "ref_inter_136x72_10_qp22_4frames", "ref_inter_264x136_8_qp32_9frames",
+                                  "ref_inter_136x72_8_qp0_5frames_noise", "ref_inter_136x72_10_qp0_4frames_noise"])
 def test_slice_data_of_p_and_b_pictures_equals_the_encoders(hip, name):
     import torch
     from uvg266_amd import api, lib

@@ -44,7 +44,12 @@ def test_device_deblocks_inter_pictures_as_the_encoder(hip, name):
             assert np.array_equal(a.cpu().numpy(), g[k][fr]), (name, fr, k)
 
 
-@pytest.mark.parametrize("name", ["ref_inter_192x128_8_qp17_5frames", "ref_inter_136x72_10_qp22_4frames"])
+@pytest.mark.parametrize("name", ["ref_inter_192x128_8_qp17_5frames", "ref_inter_136x72_10_qp22_4frames",
+                                  "ref_inter_136x72_10_qp0_4frames_noise",
+                                  # open: from coded picture 3 on, the oracle's sao_info ddistortion of CTU 1 (a SAO_TYPE_NONE decision) is a
+                                  # constant 25152 (luma) / 29633 (chroma) above the encoder's; the context models and the output picture agree
+                                  pytest.param("ref_inter_136x72_10_qp48_9frames_ra8", marks=pytest.mark.xfail(
+                                      strict=True, reason="the oracle's SAO ddistortion of one CTU differs from the encoder's at QP 51, 10 bit"))])
 def test_oracle_filters_inter_pictures_with_sao_as_the_encoder(orc, name):
     """The whole in-loop chain on P / B pictures with SAO on: per-CTU deblocking in the encoder's order (B-slice rule), the SAO
     decision of every CTU with the slice type's context initialisation and the picture's own lambda, SAO of the deblocked picture
@@ -52,12 +57,11 @@ def test_oracle_filters_inter_pictures_with_sao_as_the_encoder(orc, name):
     g = {k: v for k, v in H.ctu_golden(name).items()}
     W, Hh, depth, qp0, frames = (int(a) for a in g["dims"])
     decided = 0
+    srcs = H.golden_sources(H.ctu_golden(name))        # (coding order; every picture checked against the golden's CRCs of the encoder's input)
     for fr in range(frames):
         ks = [k for k in range(len(g["meta"])) if int(g["meta"][k][0]) == fr]
         meta = g["meta"][ks[0]]
-        src = H.moving_picture(W, Hh, fr, depth)
-        import zlib
-        assert zlib.crc32(b"".join(p.tobytes() for p in src)) == int(g["src_crc"][fr])
+        src = srcs[fr]
         slice_type = int(meta[6])                       # UVG_SLICE_B = 0, P = 1, I = 2: also the row of the initialisation table
         r = H.oracle_sao_picture(orc, depth, W, Hh, int(meta[7]), float(g["lam"][ks[0]][0]), src, (g["rec_y"][fr], g["rec_u"][fr], g["rec_v"][fr]),
                                  H.inter_scu_table(g, fr), slice_type=slice_type)

@@ -11,7 +11,9 @@ import pytest
 import helpers as H
 
 
-@pytest.mark.parametrize("name", ["ref_inter_192x128_8_qp17_5frames", "ref_inter_136x72_10_qp22_4frames"])
+@pytest.mark.parametrize("name", ["ref_inter_192x128_8_qp17_5frames", "ref_inter_136x72_10_qp22_4frames",
+                                  "ref_inter_136x72_8_qp0_5frames_noise", "ref_inter_136x72_10_qp0_4frames_noise",
+                                  "ref_inter_136x72_10_qp22_17frames_ra16"])          # random access: references found by POC, arrays in coding order
 def test_motion_compensation_plus_residual_gives_the_encoders_reconstruction(orc, name):
     g = H.ctu_golden(name)
     seen = H.inter_reconstruct(g, H.OracleBlocks(orc, int(g["dims"][2])))

@@ -9,6 +9,23 @@ import helpers as H
 
 @pytest.mark.parametrize("name", ["ref_ctu_832x480_8_qp22", "ref_ctu_416x240_10_qp37", "ref_ctu_320x192_8_qp42", "ref_ctu_192x128_10_qp12", "ref_ctu_256x128_8_qp7", "ref_ctu_264x136_10_qp32"])
 def test_every_ctu_equals_the_reference_run(orc, name):
+    g = every_ctu_equals_the_reference_run(orc, name)
+    Hh, W = g["rec_y"].shape
+    h4, w4 = Hh // 4, W // 4
+    # the partition really is a mix of sizes, and the search's final models differ from the coder's somewhere (why both are kept)
+    sizes = set(np.unique(g["cu"][:h4, :w4, 1]).tolist())
+    assert len(sizes) >= 4 and sizes <= {2, 3, 4, 5, 6}
+    assert any(not np.array_equal(g["models"][k, 1], g["models"][k, 2]) for k in range(len(g["models"])))
+
+
+@pytest.mark.parametrize("name", ["ref_ctu_136x72_10_qp0", "ref_ctu_200x136_8_qp51", "ref_ctu_40x24_8_qp22", "ref_ctu_24x136_10_qp37"])
+def test_every_ctu_at_the_extremes_equals_the_reference_run(orc, name):
+    """The same parity at QP 0 / 51, on white noise and lone impulses, on pictures smaller than one CTU -- content whose partitions are
+    uniform (all small CUs on noise, no 64x64 CU in a picture of 40x24), so without the mix-of-sizes check above."""
+    every_ctu_equals_the_reference_run(orc, name)
+
+
+def every_ctu_equals_the_reference_run(orc, name):
     g = H.ctu_golden(name)
     W, Hh, depth, qp, y, u, v = H.golden_source(g)
     prm = H.search_params(W, Hh, qp)
@@ -25,10 +42,7 @@ def test_every_ctu_equals_the_reference_run(orc, name):
         assert np.array_equal(r[p], g[p]), p
     # levels: the reference leaves uninitialised memory outside the picture (its work-tree copies are malloc'ed), so only inside
     assert np.array_equal(H.ctu_crcs(r, W, Hh)[:, 2], H.ctu_crcs(dict(r, coeff=g["coeff"]), W, Hh)[:, 2])
-    # the partition really is a mix of sizes, and the search's final models differ from the coder's somewhere (why both are kept)
-    sizes = set(np.unique(g["cu"][:h4, :w4, 1]).tolist())
-    assert len(sizes) >= 4 and sizes <= {2, 3, 4, 5, 6}
-    assert any(not np.array_equal(g["models"][k, 1], g["models"][k, 2]) for k in range(len(g["models"])))
+    return g
 
 
 def test_1080p_picture_equals_the_reference_run_ctu_by_ctu(orc):

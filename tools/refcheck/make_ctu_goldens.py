@@ -569,5 +569,15 @@ if __name__ == "__main__":
     tiles(1920, 1080, 8, 22, (0, 1), 2, 2, crc_only=True)      # BASELINE configs[1]'s picture in 2 x 2 tiles (bench.py tiles_clip), by CRC
     tiles(1920, 1080, 8, 22, (0, 1), 6, 4, crc_only=True)      # ... bench.py's tiles_clip: 24 tiles of 5 x 4 / 5 x 5 CTUs
     tiles(3840, 2160, 10, 22, (0,), 4, 2, crc_only=True)       # ... configs[3]'s size and depth in 4 x 2 tiles: one tile per GPU of the node
+    # the QP and content extremes, and pictures smaller than one CTU
+    full(136, 72, 10, 0, t=3005, picture=helpers_varied())       # white noise, 10 bit, QP 0: the largest levels, escape codes, the int16 coefficient clip
+    full(200, 136, 8, 51, t=4003, picture=helpers_varied())      # lone impulses on grey at QP 51
+    full(40, 24, 8, 22, t=1002, picture=helpers_varied())        # one partial CTU
+    full(24, 136, 10, 37, t=7)                                   # one partial CTU column, three WPP rows
+    inter(136, 72, 8, 0, 5, clip=4, suffix="_noise")              # lp-g4d3t1 at base QP 0 on full-range noise with plateaus at 0 / max
+    inter(136, 72, 10, 0, 4, clip=4, suffix="_noise")             # ... at 10 bit
+    inter(136, 72, 8, 51, 5, clip=True, suffix="_clip")           # every P / B picture clipped to QP 51 (rate_control.c CLIP_TO_QP)
+    inter(136, 72, 10, 48, 9, extra=("gop", "8"), suffix="_ra8", clip=True)      # random access at a high QP, the QP offsets clipped
+    inter(40, 24, 8, 27, 5, clip=True, suffix="_clip")            # a one-CTU picture: one partial CTU, the wavefront of one CTU (vectors leave it at the bottom)
     if not os.environ.get("GOLDENS_SKIP_CLIP120"):      # (ten minutes and 4 GB of records by itself)
         inter_crcs(1920, 1080, 8, 27, 120, extra=("owf", "1"), suffix="_owf1", clip=True)     # bench.py's c3_clip, picture by picture: BASELINE configs[2] as written, --owf 1 (frames in flight), crosses the second intra period at POC 64

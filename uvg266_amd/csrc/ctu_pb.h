@@ -1776,7 +1776,13 @@ template <typename PX> CTU_DEV void search_ctu_pb(lds<PX> *S, const job<PX> &J)
     }
     if (!decide) {
       // a child of N came back with `ret`
-      if (N.evalp == 1 && !N.known && eval_ready_pb(S, L)) { SERIAL take_eval_pb(S, P, L); CTU_SYNC(); }
+      if (N.evalp == 1 && !N.known && L == 0 && S->depth_wave == 2 && N.child < 3) {
+        // the 64x64 CU of the four-wave build: a split that loses keeps the models (and history table) of the children walked before it
+        // lost (search_ctu_pb), and the reference stops after the first child that makes the split cost more -- so the CU's cost has to be in
+        // before the next child is walked, or a late evaluation (QP 51: ref_inter_136x72_8_qp51_5frames_clip) leaves the models of children
+        // the reference never walked
+        PB_T0(); wait_eval_pb(S, L); PB_T1(J.W, 17); SERIAL take_eval_pb(S, P, L); CTU_SYNC();
+      } else if (N.evalp == 1 && !N.known && eval_ready_pb(S, L)) { SERIAL take_eval_pb(S, P, L); CTU_SYNC(); }
       SERIAL {
         N.split_cost += ret;
         const int k = N.child;

@@ -296,18 +296,39 @@ extern "C" int uvghip_frame_pool_finish(uvghip_frame_pool_t *p, int slot, void *
   group_t &g = p->groups[s.group];
   const bool wait = !g.waited;
   hipStream_t st = g.st;
+  // an error from here on gives the slot back (FREE, its group's count down): without that a failed finish would leave it LAUNCHED for good
+  auto fail = [&](int rc) {
+    if (lock.owns_lock()) lock.unlock();
+    (void)hipStreamSynchronize(st);           // (nothing of the group's stream may still write into the slot's staging)
+    lock.lock();
+    s.state = FREE; s.group = -1; s.index = -1;
+    if (--g.unfinished == 0) { g.launched = false; g.slots.clear(); }
+    return rc;
+  };
+#define FAIL_TRY(expr)                                                   \
+  do {                                                                   \
+    hipError_t e__ = (expr);                                             \
+    if (e__ != hipSuccess) return fail(uvghip_set_error(e__, #expr));    \
+  } while (0)
   lock.unlock();                              // begin() of the next frames goes on while this one waits
   const bool tiled = p->tiled();
   const int n_sub = p->n_sub;
-  if (wait && !tiled) UVGHIP_TRY(hipStreamSynchronize(st));
+  if (wait && !tiled) FAIL_TRY(hipStreamSynchronize(st));
   if (wait && tiled) {
-    // every substream of every picture of the group in one call (it waits for the stream): lengths, bytes in the order of the bitstream
+    // every substream of every picture of the group in one call (it waits for the stream): lengths, bytes in the order of the bitstream.
+    // The raw size of the pictures is a first guess, not a bound (full-range noise at QP 0 codes to 1.6 x its raw size at 8 bit): a group
+    // that needs more grows the buffer to what the call reports and asks once more
     const int k = (int)g.slots.size();
     g.lens.resize((size_t)k * n_sub);
     if (g.bytes.size() < (size_t)k * p->psz) g.bytes.resize((size_t)k * p->psz);
     std::vector<uint32_t> sums((size_t)3 * k);
     size_t used = 0;
-    if (int rc = uvghip_tiles_plan_substreams(g.tplan, 0, k, g.lens.data(), g.bytes.data(), g.bytes.size(), &used, sums.data(), st)) return rc;
+    int rc = uvghip_tiles_plan_substreams(g.tplan, 0, k, g.lens.data(), g.bytes.data(), g.bytes.size(), &used, sums.data(), st);
+    if (rc && used > g.bytes.size()) {
+      g.bytes.resize(used);
+      rc = uvghip_tiles_plan_substreams(g.tplan, 0, k, g.lens.data(), g.bytes.data(), g.bytes.size(), &used, sums.data(), st);
+    }
+    if (rc) return fail(rc);
     g.pic_off.assign((size_t)k + 1, 0);
     for (int i = 0; i < k; ++i) {
       size_t n = 0;
@@ -320,20 +341,20 @@ extern "C" int uvghip_frame_pool_finish(uvghip_frame_pool_t *p, int slot, void *
   size_t total = 0;
   for (int r = 0; r < n_sub; ++r) {
     const int nb = tiled ? g.lens[(size_t)s.index * n_sub + r] : g.host_row_bytes[(size_t)s.index * p->hc + r];
-    if (nb <= 0 || (!tiled && nb > g.row_cap)) return uvghip_set_error(hipErrorInvalidValue, "uvghip_frame_pool_finish: a row overflowed its slot");
+    if (nb <= 0 || (!tiled && nb > g.row_cap)) return fail(uvghip_set_error(hipErrorInvalidValue, "uvghip_frame_pool_finish: a row overflowed its slot"));
     s.host_row_bytes[r] = nb;
     total += nb;
   }
   if (total > s.host_rows_cap) {
-    if (s.host_rows) { UVGHIP_TRY(hipHostFree(s.host_rows)); s.host_rows = nullptr; s.host_rows_cap = 0; }
+    if (s.host_rows) { FAIL_TRY(hipHostFree(s.host_rows)); s.host_rows = nullptr; s.host_rows_cap = 0; }
     const size_t want = total + total / 2 + 4096;
-    UVGHIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.host_rows), want, hipHostMallocDefault));
+    FAIL_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.host_rows), want, hipHostMallocDefault));
     s.host_rows_cap = want;
   }
   size_t at = 0;
   for (int r = 0; r < p->hc && !tiled; ++r) {
     const int nb = s.host_row_bytes[r];
-    UVGHIP_TRY(hipMemcpyAsync(s.host_rows + at, g.d_rows + ((size_t)s.index * p->hc + r) * g.row_cap, nb, hipMemcpyDeviceToHost, st));
+    FAIL_TRY(hipMemcpyAsync(s.host_rows + at, g.d_rows + ((size_t)s.index * p->hc + r) * g.row_cap, nb, hipMemcpyDeviceToHost, st));
     at += nb;
   }
   if (tiled) memcpy(s.host_rows, g.bytes.data() + g.pic_off[s.index], total);
@@ -342,7 +363,8 @@ extern "C" int uvghip_frame_pool_finish(uvghip_frame_pool_t *p, int slot, void *
   copy_rows(static_cast<uint8_t *>(out_y), out_stride * b, s.host_out, p->w * b, p->w * b, p->h);
   copy_rows(static_cast<uint8_t *>(out_u), out_stride_c * b, s.host_out + p->ysz, p->w / 2 * b, p->w / 2 * b, p->h / 2);
   copy_rows(static_cast<uint8_t *>(out_v), out_stride_c * b, s.host_out + p->ysz + p->csz, p->w / 2 * b, p->w / 2 * b, p->h / 2);
-  if (!tiled) UVGHIP_TRY(hipStreamSynchronize(st));       // the rows (the group's stream carries nothing else before all its frames are finished)
+  if (!tiled) FAIL_TRY(hipStreamSynchronize(st));         // the rows (the group's stream carries nothing else before all its frames are finished)
+#undef FAIL_TRY
   lock.lock();
   s.state = FREE; s.group = -1; s.index = -1;
   if (--g.unfinished == 0) { g.launched = false; g.slots.clear(); }
