@@ -971,7 +971,7 @@ UVGHIP_API int uvghip_loop_plan_run(uvghip_loop_plan_t *plan, void *stream);
  * filtered when it is searched and coded when it is filtered, as encoder_state_worker_encode_lcu_search / _bitstream do CTU by CTU
  * (src/encoderstate.c:808-939), and the group's tail is one CTU's filter + its row's last bins instead of the whole filter and coder
  * launches.  Forked from and joined to `stream`.  What runs beside the search is capped (128 persistent filter workgroups, 256 persistent
- * coder waves that take row r of every picture, then row r + 1: UVGHIP_OVERLAP_FILTER_WGS / UVGHIP_OVERLAP_CODER_WAVES), because a waiting
+ * coder waves that take row r of every picture, then row r + 1), because a waiting
  * workgroup holds LDS the search cannot use.  For the latency of ONE small group: when the pictures' wavefronts can have more than 512 CTUs in
  * progress (half the device's workgroup slots: more than 30 pictures of 1080p) the call IS uvghip_loop_plan_run -- beside a search that fills
  * the device the overlap costs more search slots than the tail it hides (measured), and with several groups in flight
@@ -1430,39 +1430,22 @@ UVGHIP_API int uvghip_loop_pb_run_inflight(int bitdepth, const uvghip_loop_pb_pi
                                            void *workspace, void *stream);
 UVGHIP_API int uvghip_loop_pb_inflight_results(int bitdepth, int n_pictures, int pic_w, int pic_h, void *workspace, const int32_t **sao_info,
                                                const uint16_t **sao_models, const uint8_t **rows, const int32_t **row_bytes, int *row_cap, int *n_rows);
-/* ... with I pictures IN the flight (round 6): a picture of the call whose SEARCH runs in the all-intra launch on ANOTHER stream beside this
- * call (ext[i].searched_flags = uvghip_loop_plan_searched_flags(plan) + picture * ctus; pictures[i].search.slice_type 2, .params / .pic the
- * plan's picture, out_* its output planes).  This call runs its filter stage CTU by CTU as that launch finishes its CTUs and the P / B
- * pictures that refer to it follow four diagonals behind, as behind any other picture.  Its SAO decisions go to ext[i].sao_info /
- * sao_models (the plan's arrays, uvghip_loop_plan_results), its slice data comes from uvghip_loop_plan_run_coder afterwards.  A picture that
- * refers to it names it in ref_in_call; its ref_motion is the caller's table for an intra picture (type 1 everywhere, no vectors).
- * The caller's duties: (1) uvghip_loop_plan_search_reset on the plan's stream, an event behind it, THIS call's stream waits for the event
- * (the flags must be zero before this call's kernel can look at them), then uvghip_loop_plan_search_launch; (2) the plan's launch must be
- * small enough to run beside this call's workgroups, which take whole CUs: uvghip_loop_plan_set_search_grid(plan, G) makes it G persistent
- * workgroups, and other_workgroups = G (0..512) here leaves them their CUs (G / 4).  ext == NULL: uvghip_loop_pb_run_inflight. */
-typedef struct uvghip_inflight_external {
-  const int32_t *searched_flags;        /* DEVICE, [ctus]; NULL: an ordinary picture of the call */
-  int32_t *sao_info;                    /* DEVICE, [ctus][34] / [ctus][6]: where the picture's SAO decisions go (NULL: the call's own results) */
-  uint16_t *sao_models;
-} uvghip_inflight_external_t;
-UVGHIP_API int uvghip_loop_pb_run_inflight_ext(int bitdepth, const uvghip_loop_pb_picture_t *pictures, int n_pictures, int sao_type, const int32_t *ref_in_call,
-                                               const uvghip_inflight_external_t *ext, int other_workgroups, void *workspace, void *stream);
-/* where the in-flight launch of a call on `workspace` raises its pictures' per-CTU "final" flags ([picture][ctu], device memory): 1 when the
- * CTU's SAO decision and its part of the output picture are published.  The call zeroes them in its stream before its kernel. */
-UVGHIP_API const int32_t *uvghip_loop_pb_inflight_final_flags(int bitdepth, int n_pictures, int pic_w, int pic_h, const void *workspace);
-/* the all-intra plan's side of it: the search launch in two halves (reset: counters and flags to zero in stream order; launch), as G
- * persistent workgroups (0: one per CTU), its per-CTU "searched" flags [picture][ctu], and the slice data alone */
-UVGHIP_API int uvghip_loop_plan_search_reset(uvghip_loop_plan_t *plan, void *stream);
-UVGHIP_API int uvghip_loop_plan_search_launch(uvghip_loop_plan_t *plan, void *stream);
-UVGHIP_API int uvghip_loop_plan_set_search_grid(uvghip_loop_plan_t *plan, int max_workgroups);
-UVGHIP_API const int32_t *uvghip_loop_plan_searched_flags(const uvghip_loop_plan_t *plan);
+/* ... with the clip's I pictures IN the flight: the first entries of `pictures` are the pictures of the all-intra loop plans `intra_plans`,
+ * plan after plan, picture after picture.  The library fills those entries from the plans (the search's picture, the output planes); the
+ * caller's are ignored and may be zero.  Their search runs in the plans' own launches -- a few persistent workgroups, one per CTU a picture's
+ * wavefront can have in progress -- BESIDE the in-flight launch, which runs their filter stage CTU by CTU as they are searched, so that the
+ * P / B pictures that refer to an I picture follow it four diagonals behind, as behind any other picture.  A picture that refers to one
+ * names it in ref_in_call; its ref_motion is the caller's table for an intra picture (type 1 inside the picture, no vectors).
+ * Results: an I picture's SAO decisions and slice data are its plan's (uvghip_loop_plan_results / _slice_data; its entries of this call's
+ * result arrays stay unwritten), a P / B picture's as uvghip_loop_pb_inflight_results.  workspace:
+ * uvghip_loop_pb_inflight_workspace_bytes of ALL n_pictures.  The plans' searches and the flight run on streams of the first plan's own,
+ * forked from and joined to `stream`: work enqueued on `stream` afterwards sees all of it; nothing waits for the stream.  One such call
+ * per plan at a time.  Refused before anything is enqueued: a NULL plan, a plan whose size, bit depth or sao_type differs from the call's,
+ * fewer pictures than the plans hold, a ref_in_call entry that is not an earlier picture. */
+UVGHIP_API int uvghip_loop_pb_run_inflight_intra(int bitdepth, uvghip_loop_plan_t *const *intra_plans, int n_plans, const uvghip_loop_pb_picture_t *pictures,
+                                                 int n_pictures, int sao_type, const int32_t *ref_in_call, void *workspace, void *stream);
+/* The slice data of an all-intra plan alone, from the SAO decisions in the plan's arrays (uvghip_loop_plan_results). */
 UVGHIP_API int uvghip_loop_plan_run_coder(uvghip_loop_plan_t *plan, void *stream);
-/* ... and BESIDE the in-flight launch instead of behind it: the rows of the plan's pictures wait, CTU by CTU, for the flags that launch
- * raises when a CTU's filters are done (final_flags: [picture][ctu] of the plan's pictures inside uvghip_loop_pb_inflight_final_flags of
- * the call, i.e. + first_picture * ctus), so the I pictures' slice data is written while the P / B pictures are still searched.  Enqueue
- * it behind uvghip_loop_plan_search_launch on the same stream (the search's outputs must be complete), and zero the flags of these
- * pictures in that stream before the search launch (the in-flight call zeroes all of them again in its own stream before its kernel). */
-UVGHIP_API int uvghip_loop_plan_run_coder_behind(uvghip_loop_plan_t *plan, const int32_t *final_flags, void *stream);
 
 #ifdef __cplusplus
 }

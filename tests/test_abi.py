@@ -59,6 +59,23 @@ def test_internal_steps_stay_out_of_the_abi():
     assert not leaked, f"declared in csrc/internal.h but exported: {leaked}"
 
 
+def test_the_intra_flight_schedule_is_one_call():
+    """I pictures in the flight: the stream order belongs to uvghip_loop_pb_run_inflight_intra.  The launch halves, flag pointers and
+    the descriptor a caller once had to string together in the right order are not in the header or the export list any more."""
+    from uvg266_amd import lib
+    gone = ["uvghip_loop_plan_search_reset", "uvghip_loop_plan_search_launch", "uvghip_loop_plan_set_search_grid", "uvghip_loop_plan_searched_flags",
+            "uvghip_loop_plan_run_coder_behind", "uvghip_loop_pb_inflight_final_flags", "uvghip_loop_pb_run_inflight_ext"]
+    src = open(os.path.join(ROOT, "include", "uvg266_hip.h")).read()
+    lib.load_library()
+    out = subprocess.check_output(["nm", "-D", "--defined-only", lib.LIB_PATH], text=True)
+    exported = {line.split()[-1] for line in out.splitlines()}
+    for name in gone + ["uvghip_inflight_external"]:
+        assert name not in src and name not in lib.SIGNATURES and not any(name in s for s in exported), name
+    assert not hasattr(lib, "InflightExternal")
+    assert "uvghip_loop_pb_run_inflight_intra" in header_symbols() and "uvghip_loop_pb_run_inflight_intra" in lib.SIGNATURES
+    assert "uvghip_loop_pb_run_inflight_intra" in exported
+
+
 def test_no_cpu_fallback_without_device():
     import torch
     if torch.cuda.is_available():

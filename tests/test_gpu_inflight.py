@@ -98,3 +98,18 @@ def test_inflight_refuses_what_it_cannot_keep(hip):
     with pytest.raises(RuntimeError, match="inflight_margin"):
         loop.run()
     torch.cuda.synchronize()
+    # with the I pictures in the flight the call owns the stream order: what the host can see is refused BEFORE anything is enqueued
+    # (here a reference that is not an earlier picture of the call), and the same loop runs once the table is right again
+    loop = api.LowDelayLoop(W, Hh, depth, 1, states, src, inflight=True, inflight_margin=11, intra_in_flight=True)
+    ric = loop.order[0][1][3][0]
+    last, was = ric.shape[0] - 1, int(ric[-1, 0])
+    assert 0 <= was < last
+    ric[last, 0] = last
+    with pytest.raises(RuntimeError, match="uvghip_loop_pb_run_inflight_intra: a reference inside the call"):
+        loop.run()
+    ric[last, 0] = was
+    loop.run()
+    torch.cuda.synchronize()
+    for f in range(frames):
+        for c, nme in enumerate(("final_y", "final_u", "final_v")):
+            assert np.array_equal(loop.out[f][0][c].cpu().numpy(), g[nme][f]), (f, nme)

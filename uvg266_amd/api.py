@@ -6,7 +6,6 @@ Planes are 2-D tensors (rows x stride) of dtype uint8 (8-bit) or uint16/int16
 (10-bit); `width` is the visible width when the stride is larger.
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
@@ -1231,12 +1230,10 @@ class LowDelayLoop:
     temporal layer, and of neighbouring GOPs, run side by side on k streams (deps[f]: the coded pictures f reads)."""
 
     def __init__(self, W, H, depth, n_seq, frames, src, sao_type=3, tmvp=1, max_merge=6, merge_level=2, bipred=1, fme_level=4, early_skip=1, by_level=False, rd=0, inflight_margin=0,
-                 inflight=False, intra_in_flight=False, intra_grid=None):
-        """intra_in_flight (with inflight): the I pictures are part of the flight too -- their search runs as `intra_grid` persistent workgroups on a
-        second stream BESIDE the in-flight launch, which filters them CTU by CTU as they are searched (uvghip_loop_pb_run_inflight_ext), so the
-        P / B pictures behind an I picture follow it four diagonals behind instead of waiting for the whole picture.  intra_grid: workgroups of
-        an I group's launch (None: one per CTU its pictures' wavefronts can have in progress, min(wc, hc) per picture -- measured best: more only wait
-        and take CUs from the flight, whose workgroups need whole ones).
+                 inflight=False, intra_in_flight=False):
+        """intra_in_flight (with inflight): the I pictures are part of the flight too -- their search runs as a few persistent workgroups on a
+        second stream BESIDE the in-flight launch, which filters them CTU by CTU as they are searched (uvghip_loop_pb_run_inflight_intra), so the
+        P / B pictures behind an I picture follow it four diagonals behind instead of waiting for the whole picture.
         inflight: the encoder's --owf schedule (encoderstate.c:1060-1116): ALL P / B pictures go through ONE uvghip_loop_pb_run_inflight -- a
         picture's CTU (x, y) starts when CTU (x + 2, y + 1) of the pictures it reads is final, the in-loop filters run per CTU inside the
         search kernel -- after the I pictures (which depend on nothing).  Needs inflight_margin = 11 (9 without SAO): the vector restriction
@@ -1340,54 +1337,34 @@ class LowDelayLoop:
                 if self.steps[f][0] == "PB" and not any(st is self.steps[f] for _, st in self.order):
                     self.steps[f] = ("PB", self.steps[f][1], None, self.steps[f][3])
         self.intra_in_flight = bool(inflight and intra_in_flight)
-        if os.environ.get("UVGHIP_INTRA_GRID"):          # (development)
-            intra_grid = int(os.environ["UVGHIP_INTRA_GRID"])
         if self.intra_in_flight:
             # an intra picture as a reference: type 1 inside the picture, no vectors -- known before anything runs
-            for fl, loop, gm in igroup.values():
-                grid = int(intra_grid) if intra_grid else min(wc, hc) * loop.n
-                loop.search_grid = min(grid, loop.n * ctus)
-                if loop.n * ctus > grid:
-                    _lib.check(self.L.uvghip_loop_plan_set_search_grid(loop.loop, grid), "uvghip_loop_plan_set_search_grid")
+            groups = list(igroup.values())
+            for fl, loop, gm in groups:
                 for m in gm:
                     m.zero_()
                     m[:H // 4, :W // 4, 0] = 1
                     m[:, :, 6:8] = -1
+            # the flight's pictures: the I pictures first, plan after plan (the library fills their entries), then the P / B pictures
             pb = [f for f in range(len(frames)) if self.steps[f][0] == "PB"]
-            ent = []                                   # the flight's pictures: (kind, coded picture, sequence) -- the I pictures first
-            for fl, loop, gm in igroup.values():
+            first, n_intra = {}, 0                     # coded picture -> its first sequence's entry of the call
+            for fl, loop, gm in groups:
                 for j, f in enumerate(fl):
-                    ent += [("I", f, s_, loop, j * n_seq + s_) for s_ in range(n_seq)]
-            n_ext = len(ent)
-            ent += [("PB", f, s_, None, 0) for f in pb for s_ in range(n_seq)]
-            at = {(e[1], e[2]): i for i, e in enumerate(ent)}
-            n = len(ent)
+                    first[f] = n_intra + j * n_seq
+                n_intra += loop.n
+            for j, f in enumerate(pb):
+                first[f] = n_intra + j * n_seq
+            n = n_intra + n_seq * len(pb)
             arr = (_lib.LoopPbPicture * n)()
-            ext = (_lib.InflightExternal * n)()
             ric = np.full((n, 16), -1, np.int32)
-            a_, b_ = ctypes.c_void_p(), ctypes.c_void_p()
-            for i, (kind, f, s_, loop, idx) in enumerate(ent):
-                if kind == "I":
-                    q = arr[i]
-                    q.search.params = loop.P
-                    q.search.pic = loop.pics[idx]
-                    q.search.slice_type = 2
-                    o = loop.out[idx]
-                    q.out_y, q.out_u, q.out_v = (_dev(a) for a in o)
-                    q.out_stride, q.out_stride_c = o[0].stride(0), o[1].stride(0)
-                    _lib.check(self.L.uvghip_loop_plan_results(loop.loop, ctypes.byref(a_), ctypes.byref(b_)), "uvghip_loop_plan_results")
-                    ext[i].searched_flags = self.L.uvghip_loop_plan_searched_flags(loop.loop) + idx * ctus * 4
-                    ext[i].sao_info, ext[i].sao_models = a_.value + idx * ctus * 34 * 4, b_.value + idx * ctus * 6 * 2
-                else:
-                    ctypes.memmove(ctypes.addressof(arr) + i * ctypes.sizeof(_lib.LoopPbPicture), ctypes.addressof(self.steps[f][1]) + s_ * ctypes.sizeof(_lib.LoopPbPicture),
-                                   ctypes.sizeof(_lib.LoopPbPicture))
-                    for k in range(frames[f]["n_refs"]):
-                        g = self.ref_frame[f][k]
-                        if (g, s_) in at:
-                            ric[i, k] = at[(g, s_)]
+            for f in pb:
+                ctypes.memmove(ctypes.addressof(arr) + first[f] * ctypes.sizeof(_lib.LoopPbPicture), ctypes.addressof(self.steps[f][1]), n_seq * ctypes.sizeof(_lib.LoopPbPicture))
+                for k in range(frames[f]["n_refs"]):
+                    for s_ in range(n_seq):
+                        ric[first[f] + s_, k] = first[self.ref_frame[f][k]] + s_
             ws = z(self.L.uvghip_loop_pb_inflight_workspace_bytes(depth, n, W, H), torch.uint8)
-            grid_sum = sum(loop.search_grid for _, loop, _ in igroup.values())
-            self.order = [(list(range(len(frames))), ("FLIGHT_EXT", arr, ws, (np.ascontiguousarray(ric), ext, ent, n_ext, grid_sum, list(igroup.values()))))]
+            plans = (ctypes.c_void_p * len(groups))(*[loop.loop.value for _, loop, _ in groups])
+            self.order = [(list(range(len(frames))), ("FLIGHT_INTRA", arr, ws, (ric, plans, groups, first, pb)))]
             for f in pb:
                 self.steps[f] = ("PB", self.steps[f][1], None, self.steps[f][3])
         elif inflight:
@@ -1446,18 +1423,11 @@ class LowDelayLoop:
             else:
                 kind, arr, ws, ric = step
                 n = self.n_seq * len(fr)
-                c, d, cap, nr = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
                 if kind == "FLIGHT":
                     _lib.check(self.L.uvghip_loop_pb_run_inflight(self.depth, ctypes.byref(arr), n, self.sao_type, ric.ctypes.data, _dev(ws), st), "uvghip_loop_pb_run_inflight")
-                    _lib.check(self.L.uvghip_loop_pb_inflight_results(self.depth, n, self.W, self.H, _dev(ws), None, None, ctypes.byref(c), ctypes.byref(d), ctypes.byref(cap),
-                                                                      ctypes.byref(nr)), "uvghip_loop_pb_inflight_results")
                 else:
                     _lib.check(self.L.uvghip_loop_pb_run(self.depth, ctypes.byref(arr), n, self.sao_type, _dev(ws), st), "uvghip_loop_pb_run")
-                    _lib.check(self.L.uvghip_loop_pb_results(self.depth, n, self.W, self.H, _dev(ws), None, None, ctypes.byref(c), ctypes.byref(d), ctypes.byref(cap),
-                                                             ctypes.byref(nr)), "uvghip_loop_pb_results")
-                base = ws.data_ptr()
-                rows = ws[c.value - base:c.value - base + n * nr.value * cap.value].view(n, nr.value, cap.value)
-                row_bytes = ws[d.value - base:d.value - base + n * nr.value * 4].view(torch.int32).view(n, nr.value)
+                rows, row_bytes = self._pb_slice_data(kind, ws, n)
                 for j, g in enumerate(fr):
                     self.rows[g], self.row_bytes[g] = rows[j * self.n_seq:(j + 1) * self.n_seq], row_bytes[j * self.n_seq:(j + 1) * self.n_seq]
             if in_flight > 1:
@@ -1472,55 +1442,26 @@ class LowDelayLoop:
                 e.record(t)
                 caller.wait_event(e)
 
+    def _pb_slice_data(self, kind, ws, n):
+        """uvghip_loop_pb_results / _inflight_results of a call of n pictures on `ws` -> (rows [n, n_rows, row_cap], row_bytes [n, n_rows]) as views of it."""
+        c, d, cap, nr = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
+        name = "uvghip_loop_pb_results" if kind == "PB" else "uvghip_loop_pb_inflight_results"
+        _lib.check(getattr(self.L, name)(self.depth, n, self.W, self.H, _dev(ws), None, None, ctypes.byref(c), ctypes.byref(d), ctypes.byref(cap), ctypes.byref(nr)), name)
+        base = ws.data_ptr()
+        return (ws[c.value - base:c.value - base + n * nr.value * cap.value].view(n, nr.value, cap.value),
+                ws[d.value - base:d.value - base + n * nr.value * 4].view(torch.int32).view(n, nr.value))
+
     def _run_intra_in_flight(self, st):
-        """The I pictures' searches on stream A, the flight (their filters + every P / B picture) on stream B, both behind the caller's stream;
-        the I pictures' slice data behind the flight; the caller's stream waits for both."""
-        _, (kind, arr, ws, (ric, ext, ent, n_ext, grid_sum, groups)) = self.order[0]
-        if not hasattr(self, "_ab"):
-            self._ab = (torch.cuda.Stream(), torch.cuda.Stream())
-        A, B = self._ab
-        caller = torch.cuda.ExternalStream(st)
-        start = torch.cuda.Event()
-        start.record(caller)
-        A.wait_event(start); B.wait_event(start)
-        n = len(ent)
-        ctus = ((self.W + 63) // 64) * ((self.H + 63) // 64)
-        self.L.uvghip_loop_pb_inflight_final_flags.restype = ctypes.c_void_p
-        final = self.L.uvghip_loop_pb_inflight_final_flags(self.depth, n, self.W, self.H, _dev(ws))
-        off = final - ws.data_ptr()
-        with torch.cuda.stream(A):           # the I pictures' "final" flags: zero before their coder (behind the search, on A) can look at them
-            ws[off:off + n_ext * ctus * 4].zero_()
-        for fl, loop, gm in groups:          # flags back to zero before the flight's kernel can look at them
-            _lib.check(self.L.uvghip_loop_plan_search_reset(loop.loop, A.cuda_stream), "uvghip_loop_plan_search_reset")
-        cleared = torch.cuda.Event()
-        cleared.record(A)
-        B.wait_event(cleared)
+        """uvghip_loop_pb_run_inflight_intra: the I pictures' searches and slice data beside the flight (their filters + every P / B picture), on the
+        library's own streams behind the caller's, which waits for all of it."""
+        _, (kind, arr, ws, (ric, plans, groups, first, pb)) = self.order[0]
+        _lib.check(self.L.uvghip_loop_pb_run_inflight_intra(self.depth, plans, len(plans), ctypes.byref(arr), len(arr), self.sao_type, ric.ctypes.data, _dev(ws), st),
+                   "uvghip_loop_pb_run_inflight_intra")
+        n_seq = self.n_seq
         for fl, loop, gm in groups:
-            _lib.check(self.L.uvghip_loop_plan_search_launch(loop.loop, A.cuda_stream), "uvghip_loop_plan_search_launch")
-        _lib.check(self.L.uvghip_loop_pb_run_inflight_ext(self.depth, ctypes.byref(arr), n, self.sao_type, ric.ctypes.data, ctypes.byref(ext), grid_sum, _dev(ws), B.cuda_stream),
-                   "uvghip_loop_pb_run_inflight_ext")
-        # the I pictures' slice data: behind their search on A, BESIDE the flight -- a row waits, CTU by CTU, for the flight's filter stage
-        # (uvghip_loop_plan_run_coder_behind); the I pictures are the first entries of the call, group after group
-        first = 0
-        for fl, loop, gm in groups:
-            _lib.check(self.L.uvghip_loop_plan_run_coder_behind(loop.loop, ctypes.c_void_p(final + first * ctus * 4), A.cuda_stream), "uvghip_loop_plan_run_coder_behind")
-            first += loop.n
             rows, nb = loop.slice_data()
             for j, g in enumerate(fl):
-                self.rows[g], self.row_bytes[g] = rows[j * self.n_seq:(j + 1) * self.n_seq], nb[j * self.n_seq:(j + 1) * self.n_seq]
-        coded = torch.cuda.Event()
-        coded.record(A)
-        B.wait_event(coded)
-        c, d, cap, nr = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
-        _lib.check(self.L.uvghip_loop_pb_inflight_results(self.depth, n, self.W, self.H, _dev(ws), None, None, ctypes.byref(c), ctypes.byref(d), ctypes.byref(cap), ctypes.byref(nr)),
-                   "uvghip_loop_pb_inflight_results")
-        base = ws.data_ptr()
-        rows = ws[c.value - base:c.value - base + n * nr.value * cap.value].view(n, nr.value, cap.value)
-        row_bytes = ws[d.value - base:d.value - base + n * nr.value * 4].view(torch.int32).view(n, nr.value)
-        pb = sorted({e[1] for e in ent[n_ext:]})
-        for j, g in enumerate(pb):
-            i0 = n_ext + j * self.n_seq
-            self.rows[g], self.row_bytes[g] = rows[i0:i0 + self.n_seq], row_bytes[i0:i0 + self.n_seq]
-        done = torch.cuda.Event()
-        done.record(B)
-        caller.wait_event(done)
+                self.rows[g], self.row_bytes[g] = rows[j * n_seq:(j + 1) * n_seq], nb[j * n_seq:(j + 1) * n_seq]
+        rows, nb = self._pb_slice_data(kind, ws, len(arr))
+        for g in pb:
+            self.rows[g], self.row_bytes[g] = rows[first[g]:first[g] + n_seq], nb[first[g]:first[g] + n_seq]

@@ -6,11 +6,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cstring>
+#include <vector>
 #include "../../include/uvg266_hip.h"
 
 // ---- ctu_search.hip: an all-intra search plan's run in two halves ------------------------------------------------------------------
 // For a caller that lets ANOTHER stream's kernel wait for this plan's per-CTU flags (pictures in flight behind an I picture,
-// uvghip_loop_pb_run_inflight_ext): reset -- the counters and flags back to zero, in stream order; the other stream waits for an event
+// uvghip_loop_pb_run_inflight_intra): reset -- the counters and flags back to zero, in stream order; the other stream waits for an event
 // recorded behind it -- then launch.  uvghip_ctu_plan_run is the two in a row.
 int uvgi_ctu_plan_reset(uvghip_ctu_plan_t *pl, void *stream);
 int uvgi_ctu_plan_launch(uvghip_ctu_plan_t *pl, void *stream);
@@ -65,7 +66,7 @@ const int32_t *uvgi_filter_final_flags(int n_pictures, int pic_w, int pic_h, con
 int uvgi_search_pb_inflight(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, const uvgi_pb_filter *filters, const int32_t *ref_in_call,
                             const int32_t *const *searched_flags, int other_workgroups, int n_pictures, void *workspace, void *stream);
 // where the in-flight launch raises a picture's per-CTU "final" flags (picture i at [i * ctus]): a consumer of the finished pictures that
-// runs beside the launch waits on them (uvghip_loop_plan_run_coder_behind).  The launch zeroes them in stream order before its kernel.
+// runs beside the launch waits on them (uvgi_encode_slice_rows_behind).  The launch zeroes them in stream order before its kernel.
 const int32_t *uvgi_search_pb_inflight_final_flags(int n_pictures, int pic_w, int pic_h, const void *workspace);
 
 // ---- slice_coder.hip ------------------------------------------------------------------------------------------------------------------
@@ -84,6 +85,32 @@ int uvgi_slice_rows_prepare(const uvghip_ctu_params_t *params, const uvghip_ctu_
 int uvgi_encode_slice_rows_behind(int bitdepth, const uvghip_ctu_params_t *params, int n_pictures, const int32_t *sao_info, const uint16_t *sao_models,
                                   const int32_t *final_flags, int32_t *ticket, int max_waves, void *workspace, uint8_t *out, int row_cap,
                                   int32_t *row_bytes, void *stream);
+
+// ---- loop_plan.hip: the all-intra loop plan, for loop_pb.hip (I pictures in the flight: uvghip_loop_pb_run_inflight_intra) -------------
+struct uvghip_loop_plan {
+  int bitdepth, n, w, h, sao_type, ctus;
+  uvghip_ctu_plan_t *search;
+  std::vector<uvghip_loop_picture_t> pics;
+  // carved out of the caller's workspace
+  int32_t *sao_info;
+  uint16_t *sao_models;
+  void *coder_ws;                         // the slice coder's picture table
+  uint8_t *rows;                          // the slice data: row r of picture p at rows + (p * hc + r) * row_cap
+  int32_t *row_bytes;
+  int row_cap, hc;
+  uint32_t *sums;                         // per picture: the three plane checksums of the hash SEI (filled on demand)
+  uvghip_ctu_params_t ctu_params;
+  void *filt_ws;                          // the filter stage (uvgi_filter_run)
+  int32_t *coder_ticket;                  // uvghip_loop_plan_run_overlapped: the persistent coder's row counter
+  // two streams and three events of the plan's own for what runs BESIDE the search (uvgi_loop_plan_side_streams)
+  hipStream_t side[2] = {nullptr, nullptr};
+  hipEvent_t ev_fork = nullptr, ev_side[2] = {nullptr, nullptr};
+  // uvghip_loop_plan_group_nals: the rows of the whole group gathered on the device and brought over in one copy (grown on demand)
+  uint8_t *pack_dev = nullptr, *pack_host = nullptr;
+  size_t pack_cap = 0;
+  unsigned long long *pack_base = nullptr;    // device: [n + 1] byte offsets of the pictures in the packed buffer, then [n] row pitches
+};
+int uvgi_loop_plan_side_streams(uvghip_loop_plan *pl);
 
 // ---- the P / B slice descriptor the coder takes, from the picture's search descriptor (loop_pb.hip) -----------------------------------
 inline uvghip_slice_pb_t uvgi_slice_pb_of(const uvghip_ctu_pb_picture_t &s)

@@ -210,31 +210,24 @@ extern "C" int uvghip_loop_pb_inflight_results(int bitdepth, int n_pictures, int
   return 0;
 }
 
-extern "C" const int32_t *uvghip_loop_pb_inflight_final_flags(int bitdepth, int n_pictures, int pic_w, int pic_h, const void *workspace)
-{
-  if ((bitdepth != 8 && bitdepth != 10) || n_pictures <= 0 || pic_w <= 0 || pic_h <= 0 || !workspace) return nullptr;
-  const flight_t L = flight_of(bitdepth, n_pictures, pic_w, pic_h);
-  return uvgi_search_pb_inflight_final_flags(n_pictures, pic_w, pic_h, static_cast<const unsigned char *>(workspace) + L.search);
-}
+namespace {
+// A picture of the flight whose SEARCH runs in another launch beside it (an I picture of an all-intra plan, uvgi_ctu_plan_launch on another
+// stream): that launch's per-CTU "searched" flags [ctus] and where the picture's SAO decisions go ([ctus][34] / [ctus][6], the plan's arrays,
+// which its coder reads).
+struct external_t { const int32_t *searched_flags; int32_t *sao_info; uint16_t *sao_models; };
 
-extern "C" int uvghip_loop_pb_run_inflight(int bitdepth, const uvghip_loop_pb_picture_t *pictures, int n_pictures, int sao_type, const int32_t *ref_in_call, void *workspace,
-                                           void *stream)
-{
-  return uvghip_loop_pb_run_inflight_ext(bitdepth, pictures, n_pictures, sao_type, ref_in_call, nullptr, 0, workspace, stream);
-}
-
-// ... with pictures whose SEARCH runs in another launch beside this one (ext[i].searched_flags != NULL: an I picture of the all-intra plan,
-// uvghip_loop_plan_search_launch on another stream): this call filters them CTU by CTU as that launch finishes their CTUs, so that the
-// P / B pictures behind them are in flight behind an I picture as behind any other.  Their SAO decisions go to ext[i].sao_info / sao_models
-// (the all-intra plan's arrays: its coder, uvghip_loop_plan_run_coder, reads them); they get no slice data here.
-extern "C" int uvghip_loop_pb_run_inflight_ext(int bitdepth, const uvghip_loop_pb_picture_t *pictures, int n_pictures, int sao_type, const int32_t *ref_in_call,
-                                               const uvghip_inflight_external_t *ext, int other_workgroups, void *workspace, void *stream)
+// The flight on `stream`: the in-flight launch, then the coder over the pictures it searched.  The first n_ext pictures are searched
+// elsewhere (ext[0 .. n_ext)): the launch filters them CTU by CTU as that launch finishes their CTUs, so that the P / B pictures behind them
+// are in flight behind an I picture as behind any other; they get no slice data here.  The caller's duties (uvgi_search_pb_inflight): that
+// launch is already LAUNCHED, its flags were zeroed in stream order before this stream's position, and other_workgroups is its grid.
+int run_flight(int bitdepth, const uvghip_loop_pb_picture_t *pictures, int n_pictures, int sao_type, const int32_t *ref_in_call, const external_t *ext, int n_ext,
+               int other_workgroups, void *workspace, void *stream)
 {
   UVGHIP_REQUIRE_READY();
   UVGHIP_REQUIRE_DEPTH(bitdepth);
-  if (!pictures || n_pictures <= 0 || !workspace || !ref_in_call || sao_type < 0 || sao_type > 3) return uvghip_set_error(hipErrorInvalidValue, __func__);
+  if (!pictures || n_pictures <= 0 || !workspace || !ref_in_call || sao_type < 0 || sao_type > 3) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run_inflight");
   const int w = pictures[0].search.params.pic_w, h = pictures[0].search.params.pic_h;
-  if (w <= 0 || h <= 0) return uvghip_set_error(hipErrorInvalidValue, __func__);
+  if (w <= 0 || h <= 0) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run_inflight");
   const flight_t L = flight_of(bitdepth, n_pictures, w, h);
   unsigned char *ws = static_cast<unsigned char *>(workspace);
   const int wc = (w + 63) / 64, hc = (h + 63) / 64, ctus = wc * hc;
@@ -246,12 +239,10 @@ extern "C" int uvghip_loop_pb_run_inflight_ext(int bitdepth, const uvghip_loop_p
   std::vector<uvghip_ctu_picture_t> cp(n_pictures);
   std::vector<uvghip_slice_pb_t> sl(n_pictures);
   std::vector<const int32_t *> flags(n_pictures, nullptr);
-  std::vector<int> coded;          // the pictures this call codes (all but the externally searched ones)
   for (int i = 0; i < n_pictures; ++i) {
     const uvghip_loop_pb_picture_t &q = pictures[i];
     const uvghip_ctu_pb_picture_t &s = q.search;
     if (!q.out_y || !q.out_u || !q.out_v || q.out_stride < w || q.out_stride_c < w / 2) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run_inflight: output planes");
-    if (ext && ext[i].searched_flags) flags[i] = ext[i].searched_flags; else coded.push_back(i);
     sp[i] = s;
     uvgi_pb_filter &f = fl[i];
     unsigned char *d = ws + L.dbk + (size_t)i * planes;
@@ -259,25 +250,106 @@ extern "C" int uvghip_loop_pb_run_inflight_ext(int bitdepth, const uvghip_loop_p
     f.dbk_stride = w; f.dbk_stride_c = w / 2;
     f.out_y = q.out_y; f.out_u = q.out_u; f.out_v = q.out_v; f.out_stride = q.out_stride; f.out_stride_c = q.out_stride_c;
     f.sao_info = sao_info + (size_t)i * ctus * 34; f.sao_models = sao_models + (size_t)i * ctus * 6;
-    if (flags[i] && ext[i].sao_info && ext[i].sao_models) { f.sao_info = ext[i].sao_info; f.sao_models = ext[i].sao_models; }
+    if (i < n_ext) { flags[i] = ext[i].searched_flags; f.sao_info = ext[i].sao_info; f.sao_models = ext[i].sao_models; }
     f.sao_type = sao_type; f.reserved = 0;
     cp[i] = s.pic;
-    if (!flags[i]) sl[i] = uvgi_slice_pb_of(s);          // (the others are not coded here)
+    if (i >= n_ext) sl[i] = uvgi_slice_pb_of(s);          // (the others are not coded here)
   }
-  if (int rc = uvgi_search_pb_inflight(bitdepth, sp.data(), fl.data(), ref_in_call, ext ? flags.data() : nullptr, ext ? other_workgroups : 0, n_pictures, ws + L.search,
-                                       stream))
+  if (int rc = uvgi_search_pb_inflight(bitdepth, sp.data(), fl.data(), ref_in_call, n_ext ? flags.data() : nullptr, other_workgroups, n_pictures, ws + L.search, stream))
     return rc;
-  // the slice data of every picture in one launch (a P / B picture's models start from its own frame_qp and slice type: `params` only names the size).
-  // The coded pictures are a suffix of the call in practice (I pictures first); runs of them keep their place in the results' arrays.
-  for (size_t a = 0; a < coded.size();) {
-    size_t b = a + 1;
-    while (b < coded.size() && coded[b] == coded[b - 1] + 1) ++b;
-    const int i0 = coded[a], m = (int)(b - a);
-    if (int rc = uvghip_encode_slice_rows_pb(bitdepth, &pictures[i0].search.params, cp.data() + i0, sl.data() + i0, m, sao_type ? sao_info + (size_t)i0 * ctus * 34 : nullptr,
-                                             sao_type ? sao_models + (size_t)i0 * ctus * 6 : nullptr, ws + L.coder, ws + L.rows + (size_t)i0 * hc * L.row_cap, L.row_cap,
-                                             row_bytes + (size_t)i0 * hc, stream))
-      return rc;
-    a = b;
+  if (n_ext == n_pictures) return 0;
+  // the slice data of every picture it searched in one launch (a P / B picture's models start from its own frame_qp and slice type: `params`
+  // only names the size); they keep their place in the results' arrays
+  return uvghip_encode_slice_rows_pb(bitdepth, &pictures[n_ext].search.params, cp.data() + n_ext, sl.data() + n_ext, n_pictures - n_ext,
+                                     sao_type ? sao_info + (size_t)n_ext * ctus * 34 : nullptr, sao_type ? sao_models + (size_t)n_ext * ctus * 6 : nullptr, ws + L.coder,
+                                     ws + L.rows + (size_t)n_ext * hc * L.row_cap, L.row_cap, row_bytes + (size_t)n_ext * hc, stream);
+}
+}  // namespace
+
+extern "C" int uvghip_loop_pb_run_inflight(int bitdepth, const uvghip_loop_pb_picture_t *pictures, int n_pictures, int sao_type, const int32_t *ref_in_call, void *workspace,
+                                           void *stream)
+{
+  return run_flight(bitdepth, pictures, n_pictures, sao_type, ref_in_call, nullptr, 0, 0, workspace, stream);
+}
+
+// ---- ... with the I pictures of the clip IN the flight: searched by their all-intra plans on one stream of the first plan's own BESIDE the
+// flight on the other, which filters them CTU by CTU as they are searched; their slice data behind their search, beside the flight.  The
+// whole stream order is here; the order of the steps below is what keeps a kernel from waiting for flags that are not zero yet, or for a
+// launch that is not in the queue.
+extern "C" int uvghip_loop_pb_run_inflight_intra(int bitdepth, uvghip_loop_plan_t *const *intra_plans, int n_plans, const uvghip_loop_pb_picture_t *pictures, int n_pictures,
+                                                 int sao_type, const int32_t *ref_in_call, void *workspace, void *stream)
+{
+  UVGHIP_REQUIRE_READY();
+  UVGHIP_REQUIRE_DEPTH(bitdepth);
+  if (!intra_plans || n_plans <= 0 || !intra_plans[0] || !pictures || n_pictures <= 0 || !workspace || !ref_in_call) return uvghip_set_error(hipErrorInvalidValue, __func__);
+  uvghip_loop_plan *const p0 = intra_plans[0];
+  const int w = p0->w, h = p0->h, ctus = p0->ctus, wc = (w + 63) / 64, per = wc < p0->hc ? wc : p0->hc;
+  // everything that can be refused is refused before anything is enqueued
+  int n_intra = 0, other_workgroups = 0;
+  for (int k = 0; k < n_plans; ++k) {
+    const uvghip_loop_plan *pl = intra_plans[k];
+    if (!pl || pl->bitdepth != bitdepth || pl->w != w || pl->h != h || pl->sao_type != sao_type)
+      return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run_inflight_intra: a plan's size, bit depth or sao_type differs from the call's");
+    n_intra += pl->n;
+    // the plan's launch beside the flight, whose workgroups take whole CUs: one workgroup per CTU the pictures' wavefronts can have in progress
+    // (more only wait and take CUs from the flight), which the flight leaves the CUs for
+    other_workgroups += pl->n * (per < ctus ? per : ctus);
   }
-  return 0;
+  if (n_pictures < n_intra) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run_inflight_intra: fewer pictures than the plans hold");
+  if (other_workgroups > 512) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run_inflight_intra: the plans' launches need more than 512 workgroups");
+  for (int i = n_intra; i < n_pictures; ++i) {
+    if (pictures[i].search.params.pic_w != w || pictures[i].search.params.pic_h != h)
+      return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run_inflight_intra: a picture's size differs from the plans'");
+    for (int k = 0; k < 16 && k < pictures[i].search.n_refs; ++k)
+      if (ref_in_call[(size_t)i * 16 + k] >= i) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run_inflight_intra: a reference inside the call must be an earlier picture of it");
+  }
+  // the I entries from the plans: the search's picture, the output planes, the SAO arrays, the searched flags
+  std::vector<uvghip_loop_pb_picture_t> pics(pictures, pictures + n_pictures);
+  std::vector<external_t> ext(n_intra);
+  for (int k = 0, at = 0; k < n_plans; ++k) {
+    uvghip_loop_plan *pl = intra_plans[k];
+    if (ctus > per)          // (else the plan keeps its workgroup per CTU)
+      if (int rc = uvgi_ctu_plan_set_grid(pl->search, per * pl->n)) return rc;
+    for (int j = 0; j < pl->n; ++j, ++at) {
+      const uvghip_loop_picture_t &p = pl->pics[j];
+      uvghip_loop_pb_picture_t &q = pics[at];
+      memset(&q, 0, sizeof q);
+      q.search.params = pl->ctu_params; q.search.pic = p.search; q.search.slice_type = 2;
+      q.out_y = p.out_y; q.out_u = p.out_u; q.out_v = p.out_v; q.out_stride = p.out_stride; q.out_stride_c = p.out_stride_c;
+      ext[at] = external_t{uvgi_ctu_plan_done_flags(pl->search) + (size_t)j * ctus, pl->sao_info + (size_t)j * ctus * 34, pl->sao_models + (size_t)j * ctus * 6};
+    }
+  }
+  if (int rc = uvgi_loop_plan_side_streams(p0)) return rc;
+  hipStream_t st = uvghip_stream(stream), intra = p0->side[0], flight = p0->side[1];
+  // 1. both sides behind the caller's stream
+  UVGHIP_TRY(hipEventRecord(p0->ev_fork, st));
+  UVGHIP_TRY(hipStreamWaitEvent(intra, p0->ev_fork, 0));
+  UVGHIP_TRY(hipStreamWaitEvent(flight, p0->ev_fork, 0));
+  // 2. the I pictures' "final" flags (which their coder waits for, behind the search on the I side) and the plans' "searched" flags to zero;
+  //    the flight behind that: its kernel must not look at them before
+  const flight_t L = flight_of(bitdepth, n_pictures, w, h);
+  int32_t *final_flags = const_cast<int32_t *>(uvgi_search_pb_inflight_final_flags(n_pictures, w, h, static_cast<unsigned char *>(workspace) + L.search));
+  UVGHIP_TRY(hipMemsetAsync(final_flags, 0, (size_t)n_intra * ctus * sizeof(int32_t), intra));
+  for (int k = 0; k < n_plans; ++k)
+    if (int rc = uvgi_ctu_plan_reset(intra_plans[k]->search, intra)) return rc;
+  UVGHIP_TRY(hipEventRecord(p0->ev_side[0], intra));
+  UVGHIP_TRY(hipStreamWaitEvent(flight, p0->ev_side[0], 0));
+  // 3. the searches, in the queue BEFORE the flight that waits for them
+  for (int k = 0; k < n_plans; ++k)
+    if (int rc = uvgi_ctu_plan_launch(intra_plans[k]->search, intra)) return rc;
+  // 4. the flight: the I pictures' filters, the P / B pictures and their slice data
+  int rc = run_flight(bitdepth, pics.data(), n_pictures, sao_type, ref_in_call, ext.data(), n_intra, other_workgroups, workspace, flight);
+  // 5. the I pictures' slice data behind their search, BESIDE the flight: a row waits, CTU by CTU, for the flight's filter stage
+  //    (not when the flight was refused: nothing would raise the flags)
+  for (int k = 0, first = 0; k < n_plans && !rc; first += intra_plans[k++]->n) {
+    const uvghip_loop_plan *pl = intra_plans[k];
+    rc = uvgi_encode_slice_rows_behind(bitdepth, &pl->ctu_params, pl->n, pl->sao_info, pl->sao_models, final_flags + (size_t)first * ctus, nullptr, 0, pl->coder_ws, pl->rows,
+                                       pl->row_cap, pl->row_bytes, intra);
+  }
+  // 6. the flight waits for the I side, the caller's stream for the flight
+  UVGHIP_TRY(hipEventRecord(p0->ev_side[1], intra));
+  UVGHIP_TRY(hipStreamWaitEvent(flight, p0->ev_side[1], 0));
+  UVGHIP_TRY(hipEventRecord(p0->ev_fork, flight));
+  UVGHIP_TRY(hipStreamWaitEvent(st, p0->ev_fork, 0));
+  return rc;
 }

@@ -7,45 +7,12 @@
 #include <new>
 #include <vector>
 #include <cstring>
-#include <cstdlib>
-
-struct uvghip_loop_plan {
-  int bitdepth, n, w, h, qp, sao_type, ctus;
-  double lambda;
-  uvghip_ctu_plan_t *search;
-  std::vector<uvghip_loop_picture_t> pics;
-  // carved out of the caller's workspace
-  unsigned char *snap;                    // per picture: Y, U, V of the snapshot, tightly packed
-  uvghip_rect_t *rects_y, *rects_c;
-  int32_t *edge[3], *band[3];
-  void *decide_ws;
-  int32_t *sao_info;
-  uint16_t *sao_models;
-  uvghip_sao_param_t *params[3];
-  size_t snap_bytes;                      // of one picture
-  void *coder_ws;                         // the slice coder's picture table
-  uint8_t *rows;                          // the slice data: row r of picture p at rows + (p * hc + r) * row_cap
-  int32_t *row_bytes;
-  int row_cap, hc;
-  uint32_t *sums;                         // per picture: the three plane checksums of the hash SEI (filled on demand)
-  uvghip_ctu_params_t ctu_params;
-  int fused;                              // the filters are ONE launch behind the search (uvgi_filter_run); `snap` holds the deblocked pictures
-  void *filt_ws;
-  int32_t *coder_ticket;                  // uvghip_loop_plan_run_overlapped: the persistent coder's row counter
-  // uvghip_loop_plan_group_nals: the rows of the whole group gathered on the device and brought over in one copy (grown on demand)
-  // uvghip_loop_plan_run_overlapped: the filter stage and the coder on streams of the plan's own (created on first use)
-  hipStream_t side[2] = {nullptr, nullptr};
-  hipEvent_t ev_fork = nullptr, ev_side[2] = {nullptr, nullptr};
-  uint8_t *pack_dev = nullptr, *pack_host = nullptr;
-  size_t pack_cap = 0;
-  unsigned long long *pack_base = nullptr;    // device: [n + 1] byte offsets of the pictures in the packed buffer, then [n] row pitches
-};
 
 namespace {
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-struct layout_t { size_t search, snap, rects_y, rects_c, edge[3], band[3], decide, info, models, params[3], coder, row_bytes, rows, sums, filt, tick, total; int row_cap; };
+struct layout_t { size_t search, snap, info, models, coder, row_bytes, rows, sums, filt, tick, total; int row_cap; };
 
 layout_t layout_of(int bitdepth, int n, int w, int h)
 {
@@ -55,13 +22,8 @@ layout_t layout_of(int bitdepth, int n, int w, int h)
   auto take = [&](size_t bytes) { const size_t o = at; at = align_up(at + bytes, 256); return o; };
   L.search = take(uvghip_ctu_search_workspace_bytes(n, w, h));
   L.snap = take((size_t)n * ((size_t)w * h * 3 / 2) * b);
-  L.rects_y = take(ctus * sizeof(uvghip_rect_t));
-  L.rects_c = take(ctus * sizeof(uvghip_rect_t));
-  for (int c = 0; c < 3; ++c) { L.edge[c] = take((size_t)n * ctus * 40 * 4); L.band[c] = take((size_t)n * ctus * 64 * 4); }
-  L.decide = take(uvghip_sao_decide_workspace_bytes(n, w, h));
   L.info = take((size_t)n * ctus * 34 * 4);
   L.models = take((size_t)n * ctus * 6 * 2);
-  for (int c = 0; c < 3; ++c) L.params[c] = take((size_t)n * ctus * sizeof(uvghip_sao_param_t));
   const size_t hc = (size_t)((h + 63) / 64);
   L.row_cap = 3 * 64 * w * (int)b;        // twice the raw storage of a CTU row of 4:2:0 samples: no row of real content comes near
   L.coder = take(uvghip_slice_rows_workspace_bytes(n));
@@ -106,18 +68,9 @@ extern "C" int uvghip_loop_plan_create(int bitdepth, const uvghip_ctu_params_t *
   pl->search = nullptr;
   if (int rc = uvghip_ctu_plan_create(bitdepth, params, sp.data(), n_pictures, ws + L.search, &pl->search)) { delete pl; return rc; }
   const int wc = (w + 63) / 64, hc = (h + 63) / 64;
-  pl->bitdepth = bitdepth; pl->n = n_pictures; pl->w = w; pl->h = h; pl->qp = params->qp; pl->lambda = params->lambda; pl->sao_type = sao_type;
+  pl->bitdepth = bitdepth; pl->n = n_pictures; pl->w = w; pl->h = h; pl->sao_type = sao_type;
   pl->ctus = wc * hc;
   pl->pics.assign(pictures, pictures + n_pictures);
-  pl->snap = ws + L.snap;
-  pl->snap_bytes = (size_t)w * h * 3 / 2 * (bitdepth == 8 ? 1 : 2);
-  pl->rects_y = reinterpret_cast<uvghip_rect_t *>(ws + L.rects_y);
-  pl->rects_c = reinterpret_cast<uvghip_rect_t *>(ws + L.rects_c);
-  for (int c = 0; c < 3; ++c) {
-    pl->edge[c] = reinterpret_cast<int32_t *>(ws + L.edge[c]); pl->band[c] = reinterpret_cast<int32_t *>(ws + L.band[c]);
-    pl->params[c] = reinterpret_cast<uvghip_sao_param_t *>(ws + L.params[c]);
-  }
-  pl->decide_ws = ws + L.decide;
   pl->sao_info = reinterpret_cast<int32_t *>(ws + L.info);
   pl->sao_models = reinterpret_cast<uint16_t *>(ws + L.models);
   pl->coder_ws = ws + L.coder;
@@ -126,40 +79,22 @@ extern "C" int uvghip_loop_plan_create(int bitdepth, const uvghip_ctu_params_t *
   pl->row_cap = L.row_cap; pl->hc = hc;
   pl->sums = reinterpret_cast<uint32_t *>(ws + L.sums);
   pl->ctu_params = *params;
+  pl->filt_ws = ws + L.filt;
+  pl->coder_ticket = reinterpret_cast<int32_t *>(ws + L.tick);
   if (int rc = uvgi_slice_rows_prepare(params, sp.data(), n_pictures, pl->coder_ws, false, nullptr)) { uvghip_ctu_plan_destroy(pl->search); delete pl; return rc; }
-  // The in-loop filters as ONE launch behind the search, a workgroup per CTU (filters.hip, ctu_filter.h) -- the default;
-  // UVGHIP_LOOP_UNFUSED=1 keeps the chain of whole-picture kernels (deblock snapshot, SAO statistics, decision, deblocking in place,
-  // SAO apply: the same pictures and decisions, ~40 launches per picture).
-  {
-    const char *e = getenv("UVGHIP_LOOP_UNFUSED");
-    pl->fused = !(e && e[0] == '1');
-    pl->filt_ws = ws + L.filt;
-    pl->coder_ticket = reinterpret_cast<int32_t *>(ws + L.tick);
-    if (pl->fused) {
-      std::vector<uvgi_pb_filter> fl(n_pictures);
-      const size_t b = bitdepth == 8 ? 1 : 2, plane = (size_t)w * h * b;
-      for (int i = 0; i < n_pictures; ++i) {
-        uvgi_pb_filter &f = fl[i];
-        unsigned char *d = pl->snap + (size_t)i * pl->snap_bytes;
-        f.dbk_y = d; f.dbk_u = d + plane; f.dbk_v = d + plane + plane / 4; f.dbk_stride = w; f.dbk_stride_c = w / 2;
-        f.out_y = pictures[i].out_y; f.out_u = pictures[i].out_u; f.out_v = pictures[i].out_v; f.out_stride = pictures[i].out_stride; f.out_stride_c = pictures[i].out_stride_c;
-        f.sao_info = pl->sao_info + (size_t)i * pl->ctus * 34; f.sao_models = pl->sao_models + (size_t)i * pl->ctus * 6;
-        f.sao_type = sao_type; f.reserved = 0;
-      }
-      if (int rc = uvgi_filter_prepare(bitdepth, params, sp.data(), fl.data(), n_pictures, 2, pl->filt_ws)) { uvghip_ctu_plan_destroy(pl->search); delete pl; return rc; }
-    }
+  // The in-loop filters are ONE launch behind the search, a workgroup per CTU (filters.hip, ctu_filter.h); the deblocked pictures go to
+  // the workspace (per picture Y, U, V, tightly packed)
+  std::vector<uvgi_pb_filter> fl(n_pictures);
+  const size_t plane = (size_t)w * h * (bitdepth == 8 ? 1 : 2);
+  for (int i = 0; i < n_pictures; ++i) {
+    uvgi_pb_filter &f = fl[i];
+    unsigned char *d = ws + L.snap + (size_t)i * (plane * 3 / 2);
+    f.dbk_y = d; f.dbk_u = d + plane; f.dbk_v = d + plane + plane / 4; f.dbk_stride = w; f.dbk_stride_c = w / 2;
+    f.out_y = pictures[i].out_y; f.out_u = pictures[i].out_u; f.out_v = pictures[i].out_v; f.out_stride = pictures[i].out_stride; f.out_stride_c = pictures[i].out_stride_c;
+    f.sao_info = pl->sao_info + (size_t)i * pl->ctus * 34; f.sao_models = pl->sao_models + (size_t)i * pl->ctus * 6;
+    f.sao_type = sao_type; f.reserved = 0;
   }
-  // the CTU grids clipped to the picture: the rectangles sao_search_luma / _chroma hand to the decision (sao.c:605-668)
-  std::vector<uvghip_rect_t> ry(pl->ctus), rc(pl->ctus);
-  for (int cy = 0; cy < hc; ++cy)
-    for (int cx = 0; cx < wc; ++cx) {
-      const int x = cx * 64, y = cy * 64, bw = x + 64 > w ? w - x : 64, bh = y + 64 > h ? h - y : 64;
-      ry[cy * wc + cx] = uvghip_rect_t{x, y, bw, bh};
-      rc[cy * wc + cx] = uvghip_rect_t{x / 2, y / 2, bw / 2, bh / 2};
-    }
-  hipError_t e = hipMemcpy(pl->rects_y, ry.data(), ry.size() * sizeof(uvghip_rect_t), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(pl->rects_c, rc.data(), rc.size() * sizeof(uvghip_rect_t), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { uvghip_ctu_plan_destroy(pl->search); delete pl; return uvghip_set_error(e, "uvghip_loop_plan_create: rectangle tables"); }
+  if (int rc = uvgi_filter_prepare(bitdepth, params, sp.data(), fl.data(), n_pictures, 2, pl->filt_ws)) { uvghip_ctu_plan_destroy(pl->search); delete pl; return rc; }
   *plan_out = pl;
   return 0;
 }
@@ -172,31 +107,34 @@ extern "C" int uvghip_loop_plan_run(uvghip_loop_plan_t *pl, void *stream)
   return uvghip_loop_plan_run_filters(pl, stream);
 }
 
+// The plan's two streams and three events, created on first use (uvghip_loop_plan_run_overlapped; uvghip_loop_pb_run_inflight_intra).
+int uvgi_loop_plan_side_streams(uvghip_loop_plan *pl)
+{
+  if (pl->side[0]) return 0;
+  for (int i = 0; i < 2; ++i) {
+    UVGHIP_TRY(hipStreamCreateWithFlags(&pl->side[i], hipStreamNonBlocking));
+    UVGHIP_TRY(hipEventCreateWithFlags(&pl->ev_side[i], hipEventDisableTiming));
+  }
+  UVGHIP_TRY(hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming));
+  return 0;
+}
+
 extern "C" int uvghip_loop_plan_run_overlapped(uvghip_loop_plan_t *pl, void *stream)
 {
   UVGHIP_REQUIRE_READY();
   if (!pl) return uvghip_set_error(hipErrorInvalidValue, __func__);
-  if (!pl->fused) return uvghip_loop_plan_run(pl, stream);
   // Beside a search that fills the device the stage's workgroups and the coder's waves displace search workgroups (a CU's 160 KB of LDS are four
   // search workgroups exactly: one coder wave of 10 KB costs the CU a whole one) and the group gets SLOWER -- measured: 60 pictures of 1080p, up
   // to 1020 CTUs in progress on 1024 slots, 543 -> 621 ms; 16 pictures 484 -> 415 ms, one picture 461 -> 396 ms.  So: only while the
   // pictures' wavefronts leave half the device free.
-  {
-    const int wcx = (pl->w + 63) / 64;
-    if ((long long)pl->n * (wcx < pl->hc ? wcx : pl->hc) > 512 && !getenv("UVGHIP_OVERLAP_ALWAYS")) return uvghip_loop_plan_run(pl, stream);
-  }
+  const int overlap_max_ctus_in_progress = 512;
   // what runs beside the search is capped: a waiting filter workgroup or coder wave holds LDS a search workgroup cannot use (a coder wave 10 KB
   // of a CU's 160 KB beside four search workgroups of 40 KB: one wave costs the CU a search workgroup)
-  static const int filter_cap = [] { const char *e = getenv("UVGHIP_OVERLAP_FILTER_WGS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 128; }();
-  static const int coder_cap = [] { const char *e = getenv("UVGHIP_OVERLAP_CODER_WAVES"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 256; }();
+  const int filter_cap = 128, coder_cap = 256;
+  const int wc = (pl->w + 63) / 64, per = wc < pl->hc ? wc : pl->hc;
+  if ((long long)pl->n * per > overlap_max_ctus_in_progress) return uvghip_loop_plan_run(pl, stream);
   hipStream_t st = uvghip_stream(stream);
-  if (!pl->side[0]) {
-    for (int i = 0; i < 2; ++i) {
-      UVGHIP_TRY(hipStreamCreateWithFlags(&pl->side[i], hipStreamNonBlocking));
-      UVGHIP_TRY(hipEventCreateWithFlags(&pl->ev_side[i], hipEventDisableTiming));
-    }
-    UVGHIP_TRY(hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming));
-  }
+  if (int rc = uvgi_loop_plan_side_streams(pl)) return rc;
   // all flags to zero in `stream`, the side streams behind that; then the search, so that it is in the queue before anything waits for it
   if (int rc = uvgi_ctu_plan_reset(pl->search, stream)) return rc;
   if (int rc = uvgi_filter_reset(pl->n, pl->w, pl->h, pl->filt_ws, stream)) return rc;
@@ -205,7 +143,6 @@ extern "C" int uvghip_loop_plan_run_overlapped(uvghip_loop_plan_t *pl, void *str
   if (int rc = uvgi_ctu_plan_launch(pl->search, stream)) return rc;
   for (int i = 0; i < 2; ++i) UVGHIP_TRY(hipStreamWaitEvent(pl->side[i], pl->ev_fork, 0));
   // the filter stage: as many persistent workgroups as the pictures' wavefronts can have CTUs in progress, at most an eighth of the device
-  const int wc = (pl->w + 63) / 64, per = wc < pl->hc ? wc : pl->hc;
   long long g = (long long)per * pl->n;
   if (g > filter_cap) g = filter_cap;
   if (int rc = uvgi_filter_run(pl->bitdepth, pl->n, pl->w, pl->h, pl->filt_ws, uvgi_ctu_plan_done_flags(pl->search), (int)g, pl->side[0])) return rc;
@@ -226,68 +163,22 @@ extern "C" int uvghip_loop_plan_run_search(uvghip_loop_plan_t *pl, void *stream)
   return uvghip_ctu_plan_run(pl->search, stream);
 }
 
+// one launch for the filters of every picture, one for the slice data: every WPP row's substream from the levels, the side information and
+// the SAO decisions
 extern "C" int uvghip_loop_plan_run_filters(uvghip_loop_plan_t *pl, void *stream)
 {
   UVGHIP_REQUIRE_READY();
   if (!pl) return uvghip_set_error(hipErrorInvalidValue, __func__);
-  hipStream_t st = uvghip_stream(stream);
-  const size_t b = pl->bitdepth == 8 ? 1 : 2;
-  const int w = pl->w, h = pl->h, cw = w / 2, ch = h / 2;
-  if (pl->fused) {        // one launch for the filters of every picture, one for the slice data
-    if (int rc = uvgi_filter_run(pl->bitdepth, pl->n, w, h, pl->filt_ws, nullptr, 0, stream)) return rc;
-    return uvghip_encode_slice_rows(pl->bitdepth, &pl->ctu_params, nullptr, pl->n, pl->sao_info, pl->sao_models, pl->coder_ws, pl->rows, pl->row_cap, pl->row_bytes, stream);
-  }
-  for (int i = 0; i < pl->n; ++i) {
-    const uvghip_ctu_picture_t &p = pl->pics[i].search;
-    unsigned char *sy = pl->snap + (size_t)i * pl->snap_bytes, *su = sy + (size_t)w * h * b, *sv = su + (size_t)cw * ch * b;
-    UVGHIP_TRY(hipMemcpy2DAsync(sy, (size_t)w * b, p.rec_y, (size_t)p.rec_stride * b, (size_t)w * b, h, hipMemcpyDeviceToDevice, st));
-    UVGHIP_TRY(hipMemcpy2DAsync(su, (size_t)cw * b, p.rec_u, (size_t)p.rec_stride_c * b, (size_t)cw * b, ch, hipMemcpyDeviceToDevice, st));
-    UVGHIP_TRY(hipMemcpy2DAsync(sv, (size_t)cw * b, p.rec_v, (size_t)p.rec_stride_c * b, (size_t)cw * b, ch, hipMemcpyDeviceToDevice, st));
-    if (int rc = uvghip_deblock_frame_sao_snapshot(pl->bitdepth, sy, w, su, sv, cw, w, h, p.cu, p.cu_stride, 0, 0, 0, pl->qp, nullptr, stream)) return rc;
-    const size_t o = (size_t)i * pl->ctus;
-    if (int rc = uvghip_sao_stats_batch(pl->bitdepth, p.src_y, p.src_stride, sy, w, pl->rects_y, pl->ctus, pl->edge[0] + o * 40, pl->band[0] + o * 64, stream)) return rc;
-    if (int rc = uvghip_sao_stats_batch(pl->bitdepth, p.src_u, p.src_stride_c, su, cw, pl->rects_c, pl->ctus, pl->edge[1] + o * 40, pl->band[1] + o * 64, stream)) return rc;
-    if (int rc = uvghip_sao_stats_batch(pl->bitdepth, p.src_v, p.src_stride_c, sv, cw, pl->rects_c, pl->ctus, pl->edge[2] + o * 40, pl->band[2] + o * 64, stream)) return rc;
-  }
-  if (int rc = uvghip_sao_decide_pictures(pl->bitdepth, pl->n, w, h, pl->qp, pl->lambda, pl->sao_type, pl->edge[0], pl->band[0], pl->edge[1], pl->band[1],
-                                          pl->edge[2], pl->band[2], pl->decide_ws, pl->sao_info, pl->sao_models, pl->params[0], pl->params[1],
-                                          pl->params[2], stream))
-    return rc;
-  for (int i = 0; i < pl->n; ++i) {
-    const uvghip_loop_picture_t &q = pl->pics[i];
-    const uvghip_ctu_picture_t &p = q.search;
-    if (int rc = uvghip_deblock_frame(pl->bitdepth, p.rec_y, p.rec_stride, p.rec_u, p.rec_v, p.rec_stride_c, w, h, p.cu, p.cu_stride, 0, 0, 0, pl->qp, nullptr, stream)) return rc;
-    const size_t o = (size_t)i * pl->ctus;
-    if (int rc = uvghip_sao_apply_batch(pl->bitdepth, p.rec_y, p.rec_stride, q.out_y, q.out_stride, w, h, pl->rects_y, pl->params[0] + o, pl->ctus, stream)) return rc;
-    if (int rc = uvghip_sao_apply_batch(pl->bitdepth, p.rec_u, p.rec_stride_c, q.out_u, q.out_stride_c, cw, ch, pl->rects_c, pl->params[1] + o, pl->ctus, stream)) return rc;
-    if (int rc = uvghip_sao_apply_batch(pl->bitdepth, p.rec_v, p.rec_stride_c, q.out_v, q.out_stride_c, cw, ch, pl->rects_c, pl->params[2] + o, pl->ctus, stream)) return rc;
-  }
-  // the slice data: every WPP row's substream from the levels, the side information and the SAO decisions
-  return uvghip_encode_slice_rows(pl->bitdepth, &pl->ctu_params, nullptr, pl->n, pl->sao_info, pl->sao_models, pl->coder_ws, pl->rows, pl->row_cap,
-                                  pl->row_bytes, stream);
+  if (int rc = uvgi_filter_run(pl->bitdepth, pl->n, pl->w, pl->h, pl->filt_ws, nullptr, 0, stream)) return rc;
+  return uvghip_loop_plan_run_coder(pl, stream);
 }
 
-// ---- an all-intra plan whose pictures are filtered ELSEWHERE: the I pictures of a clip, searched here beside the in-flight P / B launch that
-// filters them CTU by CTU as they are searched (uvghip_loop_pb_run_inflight_ext) ----
-extern "C" int uvghip_loop_plan_search_reset(uvghip_loop_plan_t *pl, void *stream) { return pl ? uvgi_ctu_plan_reset(pl->search, stream) : uvghip_set_error(hipErrorInvalidValue, __func__); }
-extern "C" int uvghip_loop_plan_search_launch(uvghip_loop_plan_t *pl, void *stream) { return pl ? uvgi_ctu_plan_launch(pl->search, stream) : uvghip_set_error(hipErrorInvalidValue, __func__); }
-extern "C" int uvghip_loop_plan_set_search_grid(uvghip_loop_plan_t *pl, int max_workgroups) { return pl ? uvgi_ctu_plan_set_grid(pl->search, max_workgroups) : uvghip_set_error(hipErrorInvalidValue, __func__); }
-extern "C" const int32_t *uvghip_loop_plan_searched_flags(const uvghip_loop_plan_t *pl) { return pl ? uvgi_ctu_plan_done_flags(pl->search) : nullptr; }
 // the slice data alone (the pictures' SAO decisions are in the plan's arrays: uvghip_loop_plan_results)
 extern "C" int uvghip_loop_plan_run_coder(uvghip_loop_plan_t *pl, void *stream)
 {
   UVGHIP_REQUIRE_READY();
   if (!pl) return uvghip_set_error(hipErrorInvalidValue, __func__);
   return uvghip_encode_slice_rows(pl->bitdepth, &pl->ctu_params, nullptr, pl->n, pl->sao_info, pl->sao_models, pl->coder_ws, pl->rows, pl->row_cap, pl->row_bytes, stream);
-}
-
-// ... beside the launch that is still filtering the plan's pictures (I pictures in the flight): the rows wait for that launch's per-CTU flags
-extern "C" int uvghip_loop_plan_run_coder_behind(uvghip_loop_plan_t *pl, const int32_t *final_flags, void *stream)
-{
-  UVGHIP_REQUIRE_READY();
-  if (!pl || !final_flags) return uvghip_set_error(hipErrorInvalidValue, __func__);
-  return uvgi_encode_slice_rows_behind(pl->bitdepth, &pl->ctu_params, pl->n, pl->sao_info, pl->sao_models, final_flags, nullptr, 0, pl->coder_ws, pl->rows,
-                                       pl->row_cap, pl->row_bytes, stream);
 }
 
 extern "C" int uvghip_loop_plan_slice_data(const uvghip_loop_plan_t *pl, const uint8_t **rows, const int32_t **row_bytes, int *row_cap, int *n_rows)

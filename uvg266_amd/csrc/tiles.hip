@@ -331,7 +331,7 @@ extern "C" int uvghip_tiles_plan_run(uvghip_tiles_plan_t *pl, void *stream)
   hipStream_t st = uvghip_stream(stream);
   // up to two size classes: each class's filters and coder BESIDE its search (uvghip_loop_plan_run_overlapped; it is the serial order by
   // itself when the class's wavefronts fill the device) -- six streams in all, within what the runtime carries side by side
-  auto run_class = (pl->classes.size() <= 2 || getenv("UVGHIP_TILES_OVERLAP_ALL")) ? uvghip_loop_plan_run_overlapped : uvghip_loop_plan_run;
+  auto run_class = pl->classes.size() <= 2 ? uvghip_loop_plan_run_overlapped : uvghip_loop_plan_run;
   if (pl->classes.size() == 1) return run_class(pl->classes[0].plan, stream);
   // classes 1.. on the plan's own streams, class 0 on the caller's: a uniform grid's four classes then take four streams, what the
   // runtime's hardware queues carry side by side by default (GPU_MAX_HW_QUEUES = 4; a fifth stream shares a queue with another and the
