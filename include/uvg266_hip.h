@@ -947,11 +947,12 @@ UVGHIP_API int uvghip_ctu_search_intra(int bitdepth, const uvghip_ctu_params_t *
 /* ------------------- (5) the per-picture loop of the CTU worker as one call per group of pictures ---------------------- */
 
 /* replaces, for all-intra pictures: encoder_state_worker_encode_lcu_search for every CTU (src/encoderstate.c:808-976 minus the
- * bitstream writer) and the frame's SAO reconstruction (:256-343) -- uvghip_ctu_plan_run, then per picture
- * uvghip_deblock_frame_sao_snapshot on a copy of the reconstruction + uvghip_sao_stats_batch (Y, U, V), once
- * uvghip_sao_decide_pictures, then per picture uvghip_deblock_frame (in place on rec) + uvghip_sao_apply_batch into out.
- * A picture: the search's descriptor (outputs as described there; rec_* end up deblocked) + where the filtered picture goes --
- * the picture uvg_encoder_encode returns in pic_out / the next picture's reference.  Everything on `stream`, nothing waits.
+ * bitstream writer) and the frame's SAO reconstruction (:256-343) -- uvghip_ctu_plan_run, then ONE launch of the per-CTU filter stage
+ * over all pictures (what encoder_state_worker_encode_lcu_search does after uvg_search_lcu, encoderstate.c:841-853: deblocking,
+ * uvg_sao_search_lcu's statistics and decision, encoder_sao_reconstruct), then one launch of the arithmetic coder.
+ * A picture: the search's descriptor (outputs as described there) + where the filtered picture goes.  search.rec_* stay unfiltered; the
+ * deblocked pictures live in the workspace; out_* receive the picture uvg_encoder_encode returns (after SAO) / the next picture's
+ * reference.  Everything on `stream`, nothing waits.
  * sao_type: cfg.sao_type.  workspace: uvghip_loop_workspace_bytes of device memory, in use until the plan is destroyed.
  * uvghip_loop_plan_results: device pointers to the decisions ([picture][ctu][34] int32, the reference's two sao_info_t) and the
  * two SAO context models after every CTU's SAO syntax ([picture][ctu][6] uint16) -- what encode_sao codes. */

@@ -189,21 +189,19 @@ extern "C" int uvghip_alf_expand_tables(int bitdepth, int n_luma_aps, const int1
 
 namespace {
 struct ws_layout { size_t cls, rects_y, rects_c, set_y, set_c[2], cc_idx[2], luma_coef, luma_clip, chroma_coef, chroma_clip, cc_coef, total; int cls_stride; };
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 ws_layout layout_of(int w, int h)
 {
   const size_t n = (size_t)((w + 63) / 64) * ((h + 63) / 64);
   ws_layout L;
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t o = at; at = align_up(at + bytes, 256); return o; };
+  uvgi_carver c;
   L.cls_stride = (w + 3) / 4;
-  L.cls = take((size_t)L.cls_stride * ((h + 3) / 4));
-  L.rects_y = take(n * sizeof(uvghip_rect_t)); L.rects_c = take(n * sizeof(uvghip_rect_t));
-  L.set_y = take(n * 4); L.set_c[0] = take(n * 4); L.set_c[1] = take(n * 4); L.cc_idx[0] = take(n * 4); L.cc_idx[1] = take(n * 4);
-  L.luma_coef = take(sizeof(int16_t) * (N_FIXED + N_APS) * LN); L.luma_clip = take(sizeof(int16_t) * (N_FIXED + N_APS) * LN);
-  L.chroma_coef = take(sizeof(int16_t) * N_ALT * CCF); L.chroma_clip = take(sizeof(int16_t) * N_ALT * CCF);
-  L.cc_coef = take(sizeof(int16_t) * 2 * N_CC * CCW);
-  L.total = at;
+  L.cls = c.take((size_t)L.cls_stride * ((h + 3) / 4));
+  L.rects_y = c.take(n * sizeof(uvghip_rect_t)); L.rects_c = c.take(n * sizeof(uvghip_rect_t));
+  L.set_y = c.take(n * 4); L.set_c[0] = c.take(n * 4); L.set_c[1] = c.take(n * 4); L.cc_idx[0] = c.take(n * 4); L.cc_idx[1] = c.take(n * 4);
+  L.luma_coef = c.take(sizeof(int16_t) * (N_FIXED + N_APS) * LN); L.luma_clip = c.take(sizeof(int16_t) * (N_FIXED + N_APS) * LN);
+  L.chroma_coef = c.take(sizeof(int16_t) * N_ALT * CCF); L.chroma_clip = c.take(sizeof(int16_t) * N_ALT * CCF);
+  L.cc_coef = c.take(sizeof(int16_t) * 2 * N_CC * CCW);
+  L.total = c.at;
   return L;
 }
 }  // namespace

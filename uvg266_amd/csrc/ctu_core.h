@@ -140,15 +140,8 @@ enum { M_SIGGRP = 0, M_SIG = 4, M_PAR = 28, M_GT1 = 70, M_GT2 = 112, M_LASTX = 1
 enum { CU_NOTSET = 0, CU_INTRA = 1, CU_INTER = 2 };
 #define CTU_MAX_DOUBLE 1.7976931348623157e308
 
-// what the search reads from encoder_state_t / encoder_control_t (= uvghip_ctu_params_t, include/uvg266_hip.h)
-struct params {
-  int32_t pic_w, pic_h, qp, qp_c, depth_min, depth_max, wpp, combine_intra_cus, rough_levels, rd;       // rd: cfg.rdo, 0 or 1 (uvghip_ctu_params_t.rd)
-  double lambda, lambda_sqrt, c_lambda, cw_u, cw_v;
-  double c_lambda_tu;      // uvg_calculate_chroma_lambda (rate_control.c:1216-1233), evaluated by the host: lambda / 2^((qp - qp_c) / 3)
-};
-
-static_assert(sizeof(params) == sizeof(uvghip_ctu_params_t) && offsetof(params, rd) == offsetof(uvghip_ctu_params_t, rd) && offsetof(params, lambda) == offsetof(uvghip_ctu_params_t, lambda) &&
-              offsetof(params, c_lambda_tu) == offsetof(uvghip_ctu_params_t, c_lambda_tu), "ctu::params mirrors uvghip_ctu_params_t field by field");
+// what the search reads from encoder_state_t / encoder_control_t: the C ABI's own struct (include/uvg266_hip.h), taken as it is
+using params = uvghip_ctu_params_t;
 
 // one 4x4 unit of the CTU's side information while the search runs (the slice of cu_info_t this path reads back)
 struct cu4 {
@@ -2644,7 +2637,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV double tr_cost(lds<PX> *S, const par
   if (cb_y) coeff_bits_ += coeff_bits(S, V->cur, update, lv_of(V, 0), n, 0);
   unsigned chroma_ssd = 0;
   if (has_chroma) {
-    const unsigned ssd_u = (unsigned)((unsigned)V->red[1] * P.cw_u), ssd_v = (unsigned)((unsigned)V->red[2] * P.cw_v);
+    const unsigned ssd_u = (unsigned)((unsigned)V->red[1] * P.chroma_weight_u), ssd_v = (unsigned)((unsigned)V->red[2] * P.chroma_weight_v);
     chroma_ssd = ssd_u + ssd_v;
     chroma_bits += coeff_bits(S, V->cur, update, lv_of(V, 1), cn, 1);
     chroma_bits += coeff_bits(S, V->cur, update, lv_of(V, 2), cn, 2);
@@ -3036,7 +3029,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu4(lds<PX> *S, const job<
   }
   LF_T(12);
   LANE0 {
-    const unsigned chroma_ssd = has_chroma ? (unsigned)((unsigned)ssd_u * P.cw_u) + (unsigned)((unsigned)ssd_v * P.cw_v) : 0u;
+    const unsigned chroma_ssd = has_chroma ? (unsigned)((unsigned)ssd_u * P.chroma_weight_u) + (unsigned)((unsigned)ssd_v * P.chroma_weight_v) : 0u;
     const double trc = (unsigned)ssd_y * 1.0 + chroma_ssd * 1.0 + tbits * P.lambda;
     double cost = bits * P.lambda;
     cost += trc;
@@ -3325,7 +3318,7 @@ template <typename PX> CTU_DEV bool finish64(lds<PX> *S, const job<PX> &J)
     double d1 = 0;
     for (int i = 0; i < 4; ++i) {
       // cu_rd_cost_tr_split_accurate of the unit (tr_cost): SSDs + (luma bits + chroma bits) * lambda
-      const unsigned chroma_ssd = (unsigned)((unsigned)S->h64[i].ssd_u * P.cw_u) + (unsigned)((unsigned)S->h64[i].ssd_v * P.cw_v);
+      const unsigned chroma_ssd = (unsigned)((unsigned)S->h64[i].ssd_u * P.chroma_weight_u) + (unsigned)((unsigned)S->h64[i].ssd_v * P.chroma_weight_v);
       d1 += (unsigned)S->h64[i].ssd_y * 1.0 + chroma_ssd * 1.0 + (S->h64[i].bits_y + S->h64[i].bits) * P.lambda;
     }
     double c2 = 0;

@@ -305,3 +305,10 @@ __device__ CTUF_CALL void filter_ctu(unsigned char *smem, const filt_pic &P, con
 }
 
 }  // namespace ctuf
+
+// (host) the stage's picture from what a launcher is given (internal.h); is_b follows the slice type: 0 B / 1 P / 2 I
+inline ctuf::filt_pic uvgi_filt_pic_of(const uvgi_pb_filter &f, double lambda, int qp, int slice_type)
+{
+  return ctuf::filt_pic{f.dbk_y, f.dbk_u, f.dbk_v, f.out_y, f.out_u, f.out_v, f.dbk_stride, f.dbk_stride_c, f.out_stride, f.out_stride_c,
+                        f.sao_info, f.sao_models, lambda, f.sao_type, slice_type, qp, slice_type == 0};
+}

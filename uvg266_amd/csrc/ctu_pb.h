@@ -1235,7 +1235,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void finish_inter(lds<PX> *S, const 
     WSYNC();
     const unsigned luma_ssd = (unsigned)V->red[0];
     if (cb_y) coeff_bits_ += coeff_bits(S, V->cur, 1, lv_of(V, 0), q, 0);
-    const unsigned ssd_u = (unsigned)((unsigned)V->red[1] * P.cw_u), ssd_v = (unsigned)((unsigned)V->red[2] * P.cw_v);
+    const unsigned ssd_u = (unsigned)((unsigned)V->red[1] * P.chroma_weight_u), ssd_v = (unsigned)((unsigned)V->red[2] * P.chroma_weight_v);
     const unsigned chroma_ssd = ssd_u + ssd_v;
     chroma_bits += coeff_bits(S, V->cur, 1, lv_of(V, 1), q >> 1, 1);
     chroma_bits += coeff_bits(S, V->cur, 1, lv_of(V, 2), q >> 1, 2);

@@ -36,10 +36,10 @@ struct launch_args {
   int row0;                   // first CTU row of this launch (a band of a picture sharded by CTU rows): the row above it is complete in the buffers
 };
 
-// Four workgroups per CU at 8 bit is 40 960 B each: the dynamic image below + 4 304 B of function-scope tables (the build's .usage file
-// shows "LDS Size [bytes/block]: 4304").  One more word and the device holds three workgroups per CU instead of four (-25 %).
-static_assert(sizeof(ctu::lds<uint8_t>) + 4304 <= 40960, "the 8-bit LDS image of a CTU no longer fits four workgroups per CU");
-static_assert(!ctu::lds_cfg<uint16_t>::slim || sizeof(ctu::lds<uint16_t>) + 4304 <= 40960, "the slim 10-bit LDS image of a CTU no longer fits four workgroups per CU");
+// A workgroup's share of a CU's LDS (uvgi_search_lds_share): the dynamic image below + 4 304 B of function-scope tables (the build's
+// .usage file shows "LDS Size [bytes/block]: 4304")
+static_assert(sizeof(ctu::lds<uint8_t>) + 4304 <= uvgi_search_lds_share, "the 8-bit LDS image of a CTU no longer fits four workgroups per CU");
+static_assert(!ctu::lds_cfg<uint16_t>::slim || sizeof(ctu::lds<uint16_t>) + 4304 <= uvgi_search_lds_share, "the slim 10-bit LDS image of a CTU no longer fits four workgroups per CU");
 
 // PERSIST: a small grid of workgroups that take CTU after CTU (uvgi_ctu_plan_set_grid) -- for a few pictures whose search runs BESIDE
 // another kernel (the I pictures of a clip beside the in-flight P / B launch, which takes whole CUs): the launch then holds G workgroup
@@ -139,8 +139,6 @@ __global__ void __launch_bounds__(256, 4) ctu_search_kernel(launch_args A)
   }
 }
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // Profiling knob (tools/dev/pmc_icache.sh): UVGHIP_CTU_LDS_PAD=<bytes> pads the dynamic LDS of the search kernel so that fewer
 // workgroups fit a CU (occupancy experiments: 1 / 2 / 4 workgroups per CU).  Unset = 0; results never depend on it.
 size_t lds_pad()
@@ -149,23 +147,30 @@ size_t lds_pad()
   return pad;
 }
 
-// Scratch slots: a workgroup claims one while it runs.  2048 = 256 CUs x 8 is more than the device can hold of this kernel
-// (4 per CU); small jobs take one slot per CTU, rounded up to whole bitmap words.
-enum { MAX_SLOTS = 2048 };
+// the dynamic LDS of a launch, and its kernel: (bitdepth, PERSIST) -> the instantiation, for hipFuncSetAttribute and the one launch site
+size_t lds_bytes(int bitdepth) { return (bitdepth == 8 ? sizeof(ctu::lds<uint8_t>) : sizeof(ctu::lds<uint16_t>)) + lds_pad(); }
+const void *search_kernel(int bitdepth, bool persist)
+{
+  const void *const fn[2][2] = {{reinterpret_cast<const void *>(&ctu_search_kernel<uint8_t, false>), reinterpret_cast<const void *>(&ctu_search_kernel<uint16_t, false>)},
+                                {reinterpret_cast<const void *>(&ctu_search_kernel<uint8_t, true>), reinterpret_cast<const void *>(&ctu_search_kernel<uint16_t, true>)}};
+  return fn[persist][bitdepth != 8];
+}
+
 struct ws_layout { size_t ticket, slots, simd_load, done, order, pics, scratch, total; int n_slots; };
 ws_layout layout(int n_pictures, int pic_w, int pic_h)
 {
   const size_t ctus = (size_t)((pic_w + 63) / 64) * ((pic_h + 63) / 64), total = ctus * n_pictures;
   ws_layout L;
-  L.n_slots = (int)(total < MAX_SLOTS ? align_up(total, 32) : MAX_SLOTS);
-  L.ticket = 0;
-  L.slots = 256;
-  L.simd_load = L.slots + MAX_SLOTS / 8;
-  L.done = L.simd_load + 8 * 256 * 4 * sizeof(int32_t);
-  L.order = align_up(L.done + total * 4, 256);          // [0, order): zeroed before every run
-  L.pics = align_up(L.order + total * 4, 256);
-  L.scratch = align_up(L.pics + (size_t)n_pictures * sizeof(pic_dev), 256);
-  L.total = L.scratch + (size_t)L.n_slots * sizeof(ctu::scratch);
+  uvgi_carver c;
+  L.n_slots = (int)(total < uvgi_max_slots ? uvgi_align_up(total, 32) : uvgi_max_slots);
+  L.ticket = c.take(256);
+  L.slots = c.take(uvgi_max_slots / 8);
+  L.simd_load = c.take(uvgi_simd_counters * sizeof(int32_t));
+  L.done = c.take(total * 4);
+  L.order = c.take(total * 4);          // [0, order): zeroed before every run
+  L.pics = c.take((size_t)n_pictures * sizeof(pic_dev));
+  L.scratch = c.take((size_t)L.n_slots * sizeof(ctu::scratch));
+  L.total = c.end;
   return L;
 }
 
@@ -203,14 +208,11 @@ extern "C" int uvghip_ctu_plan_create_rows(int bitdepth, const uvghip_ctu_params
 {
   UVGHIP_REQUIRE_READY();
   UVGHIP_REQUIRE_DEPTH(bitdepth);
-  static_assert(sizeof(uvghip_ctu_params_t) == sizeof(ctu::params), "uvghip_ctu_params_t mirrors ctu::params");
   if (!params || !pictures || n_pictures <= 0 || !workspace || !plan_out) return uvghip_set_error(hipErrorInvalidValue, __func__);
   const uvghip_ctu_params_t &p = *params;
   if (p.pic_w <= 0 || p.pic_h <= 0 || (p.pic_w & 7) || (p.pic_h & 7) || p.pic_w > 64 * 255 || p.pic_h > 64 * 255 || n_pictures > 32767)
     return uvghip_set_error(hipErrorInvalidValue, "uvghip_ctu_plan_create: picture size");
-  if (p.wpp != 1 || p.depth_min < 1 || p.depth_max > 4 || p.depth_min > p.depth_max || p.rough_levels < 2 || p.rough_levels > 3 || p.qp < 0 || p.qp > 63 ||
-      p.qp_c < 0 || p.qp_c > 63 || !(p.lambda > 0) || p.rd < 0 || p.rd > 1)
-    return uvghip_set_error(hipErrorInvalidValue, "uvghip_ctu_plan_create: configuration outside the supported subset");
+  if (int rc = uvgi_check_params(p, 1, false, "uvghip_ctu_plan_create: configuration outside the supported subset")) return rc;
   // combine_intra_cus tries the first child's mode at EVERY depth without a search of its own (search.c:2082-2143); the kernel builds the
   // candidate at depth 0 only, which is all there is with pu-depth-intra starting at 1 (tests/test_ctu_emulation.py, other ranges)
   if (p.combine_intra_cus && p.depth_min > 1)
@@ -232,10 +234,8 @@ extern "C" int uvghip_ctu_plan_create_rows(int bitdepth, const uvghip_ctu_params
   std::vector<pic_dev> pics(n_pictures);
   for (int i = 0; i < n_pictures; ++i) {
     const uvghip_ctu_picture_t &q = pictures[i];
-    if (!q.src_y || !q.src_u || !q.src_v || !q.rec_y || !q.rec_u || !q.rec_v || !q.cu || !q.coeff || !q.models || q.cu_stride < wc * 16)
-      return uvghip_set_error(hipErrorInvalidValue, "uvghip_ctu_plan_create: picture descriptor");
-    if (q.src_stride < p.pic_w || q.rec_stride < p.pic_w || q.src_stride_c < p.pic_w / 2 || q.rec_stride_c < p.pic_w / 2)
-      return uvghip_set_error(hipErrorInvalidValue, "uvghip_ctu_plan_create: a sample stride is smaller than the picture");
+    if (int rc = uvgi_check_picture(q, p.pic_w, wc, true, "uvghip_ctu_plan_create: picture descriptor", "uvghip_ctu_plan_create: a sample stride is smaller than the picture"))
+      return rc;
     pics[i] = pic_dev{q.src_y, q.src_u, q.src_v, q.rec_y, q.rec_u, q.rec_v, q.cu, q.coeff, q.models,
                       q.src_stride, q.src_stride_c, q.rec_stride, q.rec_stride_c, q.cu_stride, 0};
   }
@@ -243,7 +243,7 @@ extern "C" int uvghip_ctu_plan_create_rows(int bitdepth, const uvghip_ctu_params
   UVGHIP_TRY(hipMemcpy(ws + L.pics, pics.data(), (size_t)n_pictures * sizeof(pic_dev), hipMemcpyHostToDevice));
   uvghip_ctu_plan *pl = new (std::nothrow) uvghip_ctu_plan;
   if (!pl) return uvghip_set_error(hipErrorOutOfMemory, __func__);
-  memcpy(&pl->A.P, params, sizeof pl->A.P);
+  pl->A.P = p;
   pl->A.pics = reinterpret_cast<const pic_dev *>(ws + L.pics);
   pl->A.order = reinterpret_cast<const int32_t *>(ws + L.order);
   pl->A.ticket = reinterpret_cast<int32_t *>(ws + L.ticket);
@@ -254,15 +254,10 @@ extern "C" int uvghip_ctu_plan_create_rows(int bitdepth, const uvghip_ctu_params
   pl->A.n_slots = L.n_slots;
   pl->A.wc = wc; pl->A.hc = hc; pl->A.n_ctus = total; pl->A.row0 = ctu_row0;
   pl->bitdepth = bitdepth; pl->total = total; pl->counters = L.order; pl->ws = ws; pl->grid = 0;
-  const size_t lds = (bitdepth == 8 ? sizeof(ctu::lds<uint8_t>) : sizeof(ctu::lds<uint16_t>)) + lds_pad();
-  const hipError_t e = bitdepth == 8
-      ? hipFuncSetAttribute(reinterpret_cast<const void *>(&ctu_search_kernel<uint8_t, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-      : hipFuncSetAttribute(reinterpret_cast<const void *>(&ctu_search_kernel<uint16_t, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) { delete pl; return uvghip_set_error(e, "uvghip_ctu_plan_create: dynamic LDS size"); }
-  const hipError_t e2 = bitdepth == 8
-      ? hipFuncSetAttribute(reinterpret_cast<const void *>(&ctu_search_kernel<uint8_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-      : hipFuncSetAttribute(reinterpret_cast<const void *>(&ctu_search_kernel<uint16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e2 != hipSuccess) { delete pl; return uvghip_set_error(e2, "uvghip_ctu_plan_create: dynamic LDS size"); }
+  for (int persist = 0; persist < 2; ++persist) {
+    const hipError_t e = hipFuncSetAttribute(search_kernel(bitdepth, persist), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(bitdepth));
+    if (e != hipSuccess) { delete pl; return uvghip_set_error(e, "uvghip_ctu_plan_create: dynamic LDS size"); }
+  }
   *plan_out = pl;
   return 0;
 }
@@ -279,14 +274,9 @@ int uvgi_ctu_plan_launch(uvghip_ctu_plan_t *pl, void *stream)
   UVGHIP_REQUIRE_READY();
   if (!pl) return uvghip_set_error(hipErrorInvalidValue, __func__);
   hipStream_t st = uvghip_stream(stream);
-  const size_t lds = (pl->bitdepth == 8 ? sizeof(ctu::lds<uint8_t>) : sizeof(ctu::lds<uint16_t>)) + lds_pad();
-  if (pl->grid > 0 && pl->grid < pl->total) {
-    if (pl->bitdepth == 8) hipLaunchKernelGGL((ctu_search_kernel<uint8_t, true>), dim3(pl->grid), dim3(256), lds, st, pl->A);
-    else hipLaunchKernelGGL((ctu_search_kernel<uint16_t, true>), dim3(pl->grid), dim3(256), lds, st, pl->A);
-  } else {
-    if (pl->bitdepth == 8) hipLaunchKernelGGL((ctu_search_kernel<uint8_t, false>), dim3(pl->total), dim3(256), lds, st, pl->A);
-    else hipLaunchKernelGGL((ctu_search_kernel<uint16_t, false>), dim3(pl->total), dim3(256), lds, st, pl->A);
-  }
+  const bool persist = pl->grid > 0 && pl->grid < pl->total;
+  void *args[] = {&pl->A};
+  (void)hipLaunchKernel(search_kernel(pl->bitdepth, persist), dim3(persist ? pl->grid : pl->total), dim3(256), args, lds_bytes(pl->bitdepth), st);
   UVGHIP_CHECK_LAUNCH();
 }
 extern "C" int uvghip_ctu_plan_run(uvghip_ctu_plan_t *pl, void *stream)

@@ -49,7 +49,7 @@ struct pb_launch_args {
 };
 
 // four workgroups (= four waves: the kernel's registers allow one per SIMD) per CU at 8 bit: 160 KB / 4 incl. the 4288 bytes of static tables
-static_assert(ctu::pb_lds_bytes<uint8_t>(1) + 4288 <= 40960, "the 8-bit LDS image of a P / B CTU no longer fits four workgroups per CU");
+static_assert(ctu::pb_lds_bytes<uint8_t>(1) + 4288 <= uvgi_search_lds_share, "the 8-bit LDS image of a P / B CTU no longer fits four workgroups per CU");
 // NT = 64: one wave walks the CTU (four workgroups per CU: many independent pictures side by side).  NT = 128: the walk's wave + the leaf
 // wave that takes the 4x4 CUs of every 8x8 area (ctu_pb.h post_leaves) -- a shorter CTU for pictures in flight behind each other, where
 // the CTU's latency, not the device's occupancy, sets the pace.
@@ -172,6 +172,15 @@ __global__ void __launch_bounds__(NT) ctu_search_pb_kernel(pb_launch_args A)
   if (threadIdx.x == 0) atomicAnd(&A.slots[s_slot >> 5], ~(1u << (s_slot & 31)));
 }
 
+// (bitdepth, waves) -> the instantiation, block size 64 * waves: for hipFuncSetAttribute and the one launch site
+template <typename PX, int NT> const void *pb_kernel() { return reinterpret_cast<const void *>(&ctu_search_pb_kernel<PX, NT>); }
+const void *search_pb_kernel(int bitdepth, int waves)
+{
+  const void *const fn[2][4] = {{pb_kernel<uint8_t, 64>(), pb_kernel<uint8_t, 128>(), pb_kernel<uint8_t, 192>(), pb_kernel<uint8_t, 256>()},
+                                {pb_kernel<uint16_t, 64>(), pb_kernel<uint16_t, 128>(), pb_kernel<uint16_t, 192>(), pb_kernel<uint16_t, 256>()}};
+  return fn[bitdepth != 8][waves - 1];
+}
+
 // The hand-out order, written on the device (stream-ordered: no host copy to wait for): index cx + 2 * cy first -- left, upper and
 // upper-right neighbours all have a smaller one --, pictures interleaved.  One block.
 __global__ void __launch_bounds__(256) pb_order_kernel(int32_t *order, int wc, int hc, int n_pictures)
@@ -225,33 +234,32 @@ __global__ void __launch_bounds__(256) pb_order_levels_kernel(int32_t *order, in
     }
   }
 }
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-enum { MAX_SLOTS = 2048 };
 struct ws_layout { size_t ticket, slots, done, hmvp, sao_done, final_done, key_cnt, key_cur, order, pics, filt, times, scratch, total; int n_slots, n_keys; };
 ws_layout layout(int n_pictures, int pic_w, int pic_h)
 {
   const size_t wc = (size_t)((pic_w + 63) / 64), hc = (size_t)((pic_h + 63) / 64), ctus = wc * hc, total = ctus * n_pictures;
   ws_layout L;
-  L.n_slots = (int)(total < MAX_SLOTS ? align_up(total, 32) : MAX_SLOTS);
+  uvgi_carver c;
+  L.n_slots = (int)(total < uvgi_max_slots ? uvgi_align_up(total, 32) : uvgi_max_slots);
   L.n_keys = (int)(wc + 2 * (hc - 1)) + LAG * n_pictures;
-  L.ticket = 0;
-  L.slots = 256;
-  L.done = L.slots + MAX_SLOTS / 8;
-  L.hmvp = align_up(L.done + total * 4, 256);
-  L.sao_done = align_up(L.hmvp + (size_t)n_pictures * hc * 41 * 4, 256);
+  L.ticket = c.take(256);
+  L.slots = c.take(uvgi_max_slots / 8);
+  L.done = c.take(total * 4);
+  L.hmvp = c.take((size_t)n_pictures * hc * 41 * 4);
+  L.sao_done = c.take(2 * total * 4 + 2 * (size_t)L.n_keys * 4);          // one piece: the two flag arrays, the two key arrays
   L.final_done = L.sao_done + total * 4;
   L.key_cnt = L.final_done + total * 4;
   L.key_cur = L.key_cnt + (size_t)L.n_keys * 4;
-  L.order = align_up(L.key_cur + (size_t)L.n_keys * 4, 256);                  // [0, order): zeroed before every run
-  L.pics = align_up(L.order + total * 4, 256);
-  L.filt = align_up(L.pics + (size_t)n_pictures * sizeof(pb_pic_dev), 256);
-  L.times = align_up(L.filt + (size_t)n_pictures * sizeof(ctuf::filt_pic), 256);
+  L.order = c.take(total * 4);                  // [0, order): zeroed before every run
+  L.pics = c.take((size_t)n_pictures * sizeof(pb_pic_dev));
+  L.filt = c.take((size_t)n_pictures * sizeof(ctuf::filt_pic));
 #if defined(CTU_PROFILE)
-  L.scratch = align_up(L.times + total * 32, 256);
+  L.times = c.take(total * 32);
 #else
-  L.scratch = L.times;
+  L.times = c.at;
 #endif
-  L.total = L.scratch + (size_t)L.n_slots * sizeof(ctu::scratch);
+  L.scratch = c.take((size_t)L.n_slots * sizeof(ctu::scratch));
+  L.total = c.end;
   return L;
 }
 
@@ -292,7 +300,7 @@ extern "C" int uvghip_ctu_search_pb(int bitdepth, const uvghip_ctu_pb_picture_t 
 int uvgi_search_pb_inflight(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, const uvgi_pb_filter *filters, const int32_t *ref_in_call,
                             const int32_t *const *searched_flags, int other_workgroups, int n_pictures, void *workspace, void *stream)
 {
-  if (!filters || !ref_in_call || other_workgroups < 0 || other_workgroups > 512 || (!searched_flags && other_workgroups)) return uvghip_set_error(hipErrorInvalidValue, __func__);
+  if (!filters || !ref_in_call || other_workgroups < 0 || other_workgroups > uvgi_flight_other_max || (!searched_flags && other_workgroups)) return uvghip_set_error(hipErrorInvalidValue, __func__);
   return search_pb(bitdepth, pictures, n_pictures, filters, ref_in_call, searched_flags, other_workgroups, workspace, stream);
 }
 
@@ -302,7 +310,6 @@ int search_pb(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, int n_pictu
 {
   UVGHIP_REQUIRE_READY();
   UVGHIP_REQUIRE_DEPTH(bitdepth);
-  static_assert(sizeof(uvghip_ctu_params_t) == sizeof(ctu::params), "uvghip_ctu_params_t mirrors ctu::params");
   if (!pictures || n_pictures <= 0 || !workspace || n_pictures > 32767) return uvghip_set_error(hipErrorInvalidValue, __func__);
   const uvghip_ctu_params_t &p0 = pictures[0].params;
   if (p0.pic_w <= 0 || p0.pic_h <= 0 || (p0.pic_w & 7) || (p0.pic_h & 7) || p0.pic_w > 64 * 255 || p0.pic_h > 64 * 255)
@@ -316,29 +323,21 @@ int search_pb(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, int n_pictu
     const uvghip_ctu_pb_picture_t &q = pictures[i];
     const uvghip_ctu_params_t &p = q.params;
     if (p.pic_w != p0.pic_w || p.pic_h != p0.pic_h) return uvghip_set_error(hipErrorInvalidValue, "uvghip_ctu_search_pb: the pictures of a call share one size");
-    if (p.wpp != 1 || p.depth_min < 1 || p.depth_max != 4 || p.depth_min > p.depth_max || p.rough_levels < 2 || p.rough_levels > 3 || p.qp < 0 || p.qp > 63 ||
-        p.qp_c < 0 || p.qp_c > 63 || !(p.lambda > 0) || !(p.lambda_sqrt > 0) || p.rd < 0 || p.rd > 1)
-      return uvghip_set_error(hipErrorInvalidValue, "uvghip_ctu_search_pb: configuration outside the supported subset");
+    if (int rc = uvgi_check_params(p, 4, true, "uvghip_ctu_search_pb: configuration outside the supported subset")) return rc;
     if (searched_flags && searched_flags[i]) {
       // a picture searched elsewhere (an I picture in uvgi_ctu_plan_launch beside this call): the filter stage only, behind that launch's flags
       const uvghip_ctu_picture_t &c = q.pic;
-      if (!filters || !c.src_y || !c.src_u || !c.src_v || !c.rec_y || !c.rec_u || !c.rec_v || !c.cu || c.cu_stride < wc * 16 || c.src_stride < p.pic_w || c.rec_stride < p.pic_w ||
-          c.src_stride_c < p.pic_w / 2 || c.rec_stride_c < p.pic_w / 2 || q.slice_type != 2 || p.qp_c != p.qp)
-        return uvghip_set_error(hipErrorInvalidValue, "uvgi_search_pb_inflight: an externally searched picture");
-      const uvgi_pb_filter &f = filters[i];
-      if (!f.dbk_y || !f.dbk_u || !f.dbk_v || !f.out_y || !f.out_u || !f.out_v || f.dbk_stride < p.pic_w || f.dbk_stride_c < p.pic_w / 2 || f.out_stride < p.pic_w ||
-          f.out_stride_c < p.pic_w / 2 || f.sao_type < 0 || f.sao_type > 3 || (f.sao_type && (!f.sao_info || !f.sao_models)))
-        return uvghip_set_error(hipErrorInvalidValue, "uvgi_search_pb_inflight: filter stage");
+      const char *const what = "uvgi_search_pb_inflight: an externally searched picture";
+      if (!filters || q.slice_type != 2 || p.qp_c != p.qp) return uvghip_set_error(hipErrorInvalidValue, what);
+      if (int rc = uvgi_check_picture(c, p.pic_w, wc, false, what)) return rc;
+      if (int rc = uvgi_check_filter(filters[i], p.pic_w, "uvgi_search_pb_inflight: filter stage")) return rc;
       pb_pic_dev &d = pics[i];
       memset(&d, 0, sizeof d);
-      memcpy(&d.P, &p, sizeof d.P);
+      d.P = p;
       d.src_y = c.src_y; d.src_u = c.src_u; d.src_v = c.src_v; d.rec_y = c.rec_y; d.rec_u = c.rec_u; d.rec_v = c.rec_v; d.cu = c.cu;
       d.src_stride = c.src_stride; d.src_stride_c = c.src_stride_c; d.rec_stride = c.rec_stride; d.rec_stride_c = c.rec_stride_c; d.cu_stride = c.cu_stride;
       d.ext_done = searched_flags[i];
-      ctuf::filt_pic &g = filt[i];
-      g.dbk_y = f.dbk_y; g.dbk_u = f.dbk_u; g.dbk_v = f.dbk_v; g.out_y = f.out_y; g.out_u = f.out_u; g.out_v = f.out_v;
-      g.dbk_stride = f.dbk_stride; g.dbk_stride_c = f.dbk_stride_c; g.out_stride = f.out_stride; g.out_stride_c = f.out_stride_c;
-      g.sao_info = f.sao_info; g.sao_models = f.sao_models; g.lambda = p.lambda; g.sao_type = f.sao_type; g.slice_type = 2; g.qp = p.qp; g.is_b = 0;
+      filt[i] = uvgi_filt_pic_of(filters[i], p.lambda, p.qp, 2);
       continue;
     }
     if ((q.slice_type != 0 && q.slice_type != 1) || q.n_refs < 1 || q.n_refs > 16 || q.l_size[0] < 1 || q.l_size[0] > 8 || q.l_size[1] < 0 || q.l_size[1] > 8 ||
@@ -346,13 +345,12 @@ int search_pb(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, int n_pictu
         q.fme_level > 4 || q.merge_level < 2)
       return uvghip_set_error(hipErrorInvalidValue, "uvghip_ctu_search_pb: slice state outside the supported subset");
     const uvghip_ctu_picture_t &c = q.pic;
-    if (!c.src_y || !c.src_u || !c.src_v || !c.rec_y || !c.rec_u || !c.rec_v || !c.cu || !c.coeff || !c.models || c.cu_stride < wc * 16 || !q.inter4 ||
-        !q.models_inter || c.src_stride < p.pic_w || c.rec_stride < p.pic_w || c.src_stride_c < p.pic_w / 2 || c.rec_stride_c < p.pic_w / 2 ||
-        q.ref_stride < p.pic_w || q.ref_stride_c < p.pic_w / 2 || q.ref_motion_stride < wc * 16)
+    if (int rc = uvgi_check_picture(c, p.pic_w, wc, true, "uvghip_ctu_search_pb: picture descriptor")) return rc;
+    if (!q.inter4 || !q.models_inter || q.ref_stride < p.pic_w || q.ref_stride_c < p.pic_w / 2 || q.ref_motion_stride < wc * 16)
       return uvghip_set_error(hipErrorInvalidValue, "uvghip_ctu_search_pb: picture descriptor");
     pb_pic_dev &d = pics[i];
     memset(&d, 0, sizeof d);
-    memcpy(&d.P, &p, sizeof d.P);
+    d.P = p;
     ctu::pb_job &B = d.B;
     B.slice_type = q.slice_type; B.poc = q.poc; B.n_refs = q.n_refs;
     for (int k = 0; k < 16; ++k) {
@@ -378,9 +376,7 @@ int search_pb(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, int n_pictu
     if (filters) {
       // the picture's references inside this call (pictures are in coding order: a reference is an earlier entry), its depth in that DAG
       const uvgi_pb_filter &f = filters[i];
-      if (!f.dbk_y || !f.dbk_u || !f.dbk_v || !f.out_y || !f.out_u || !f.out_v || f.dbk_stride < p.pic_w || f.dbk_stride_c < p.pic_w / 2 || f.out_stride < p.pic_w ||
-          f.out_stride_c < p.pic_w / 2 || f.sao_type < 0 || f.sao_type > 3 || (f.sao_type && (!f.sao_info || !f.sao_models)))
-        return uvghip_set_error(hipErrorInvalidValue, "uvgi_search_pb_inflight: filter stage");
+      if (int rc = uvgi_check_filter(f, p.pic_w, "uvgi_search_pb_inflight: filter stage")) return rc;
       if (p.qp_c != p.qp || p.qp != q.frame_qp) return uvghip_set_error(hipErrorInvalidValue, "uvgi_search_pb_inflight: qp_c != qp or params.qp != frame_qp");
       d.n_wait = 0; d.level = 0;
       for (int k = 0; k < q.n_refs; ++k) {
@@ -399,10 +395,7 @@ int search_pb(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, int n_pictu
         if (!seen) d.wait_pic[d.n_wait++] = r;
         if (pics[r].level + 1 > d.level) d.level = pics[r].level + 1;
       }
-      ctuf::filt_pic &g = filt[i];
-      g.dbk_y = f.dbk_y; g.dbk_u = f.dbk_u; g.dbk_v = f.dbk_v; g.out_y = f.out_y; g.out_u = f.out_u; g.out_v = f.out_v;
-      g.dbk_stride = f.dbk_stride; g.dbk_stride_c = f.dbk_stride_c; g.out_stride = f.out_stride; g.out_stride_c = f.out_stride_c;
-      g.sao_info = f.sao_info; g.sao_models = f.sao_models; g.lambda = p.lambda; g.sao_type = f.sao_type; g.slice_type = q.slice_type; g.qp = p.qp; g.is_b = q.slice_type == 0;
+      filt[i] = uvgi_filt_pic_of(f, p.lambda, p.qp, q.slice_type);
     }
   }
   // the hand-out order and the pictures' descriptors, in stream order (nothing here waits for the stream: a caller with independent
@@ -432,33 +425,21 @@ int search_pb(int bitdepth, const uvghip_ctu_pb_picture_t *pictures, int n_pictu
   int waves = filters ? 4 : 1;
   if (const char *e = getenv("UVGHIP_PB_WAVES")) waves = e[0] >= '1' && e[0] <= '4' ? e[0] - '0' : waves;
   const size_t lds = bitdepth == 8 ? ctu::pb_lds_bytes<uint8_t>(waves) : ctu::pb_lds_bytes<uint16_t>(waves);
-  const void *fn8[4] = {reinterpret_cast<const void *>(&ctu_search_pb_kernel<uint8_t, 64>), reinterpret_cast<const void *>(&ctu_search_pb_kernel<uint8_t, 128>),
-                        reinterpret_cast<const void *>(&ctu_search_pb_kernel<uint8_t, 192>), reinterpret_cast<const void *>(&ctu_search_pb_kernel<uint8_t, 256>)};
-  const void *fn10[4] = {reinterpret_cast<const void *>(&ctu_search_pb_kernel<uint16_t, 64>), reinterpret_cast<const void *>(&ctu_search_pb_kernel<uint16_t, 128>),
-                         reinterpret_cast<const void *>(&ctu_search_pb_kernel<uint16_t, 192>), reinterpret_cast<const void *>(&ctu_search_pb_kernel<uint16_t, 256>)};
-  const hipError_t e = hipFuncSetAttribute(bitdepth == 8 ? fn8[waves - 1] : fn10[waves - 1], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  const void *const kernel = search_pb_kernel(bitdepth, waves);
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return uvghip_set_error(e, "uvghip_ctu_search_pb: dynamic LDS size");
   // workgroups: twice the CTUs a picture's wavefront can have in progress (the widest diagonal of cx + 2 cy), per picture.  Pictures in
   // flight behind each other: a picture follows its reference LAG diagonals later, so a chain holds a picture's CTUs / LAG in progress
   // whatever its length -- a device's worth of workgroups is plenty (the rest would only wait)
   const int width = (wc + 1) / 2 < hc ? (wc + 1) / 2 : hc;
   long long want = 2LL * width * n_pictures;
-  if (filters && want > (waves >= 3 ? 256 : 1024 / waves)) want = waves >= 3 ? 256 : 1024 / waves;
+  if (filters && want > uvgi_flight_grid_cap(waves)) want = uvgi_flight_grid_cap(waves);
   // a launch that runs BESIDE this one and is waited for (externally searched pictures): this launch's workgroups take whole CUs and
-  // must leave that one its own -- four of its workgroups fit a CU
-  if (searched_flags && other_workgroups > 0 && waves >= 3) { const int room = 256 - (other_workgroups + 3) / 4; if (want > room) want = room > 16 ? room : 16; }
+  // must leave that one its own
+  if (searched_flags && other_workgroups > 0 && waves >= 3) { const int room = uvgi_flight_room(other_workgroups); if (want > room) want = room > uvgi_flight_min_grid ? room : uvgi_flight_min_grid; }
   const int grid = (int)(want < total ? want : total);
-  if (bitdepth == 8) {
-    if (waves == 4) hipLaunchKernelGGL((ctu_search_pb_kernel<uint8_t, 256>), dim3(grid), dim3(256), lds, st, A);
-    else if (waves == 3) hipLaunchKernelGGL((ctu_search_pb_kernel<uint8_t, 192>), dim3(grid), dim3(192), lds, st, A);
-    else if (waves == 2) hipLaunchKernelGGL((ctu_search_pb_kernel<uint8_t, 128>), dim3(grid), dim3(128), lds, st, A);
-    else hipLaunchKernelGGL((ctu_search_pb_kernel<uint8_t, 64>), dim3(grid), dim3(64), lds, st, A);
-  } else {
-    if (waves == 4) hipLaunchKernelGGL((ctu_search_pb_kernel<uint16_t, 256>), dim3(grid), dim3(256), lds, st, A);
-    else if (waves == 3) hipLaunchKernelGGL((ctu_search_pb_kernel<uint16_t, 192>), dim3(grid), dim3(192), lds, st, A);
-    else if (waves == 2) hipLaunchKernelGGL((ctu_search_pb_kernel<uint16_t, 128>), dim3(grid), dim3(128), lds, st, A);
-    else hipLaunchKernelGGL((ctu_search_pb_kernel<uint16_t, 64>), dim3(grid), dim3(64), lds, st, A);
-  }
+  void *args[] = {&A};
+  (void)hipLaunchKernel(kernel, dim3(grid), dim3(64 * waves), args, lds, st);
   UVGHIP_CHECK_LAUNCH();
 }
 }  // namespace

@@ -72,17 +72,24 @@ __global__ void __launch_bounds__(256) ctu_filter_kernel(filter_args A)
   }
 }
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// (bitdepth, BEHIND) -> the instantiation: the one launch site's kernel
+const void *filter_kernel(int bitdepth, bool behind)
+{
+  const void *const fn[2][2] = {{reinterpret_cast<const void *>(&ctu_filter_kernel<uint8_t, true>), reinterpret_cast<const void *>(&ctu_filter_kernel<uint16_t, true>)},
+                                {reinterpret_cast<const void *>(&ctu_filter_kernel<uint8_t, false>), reinterpret_cast<const void *>(&ctu_filter_kernel<uint16_t, false>)}};
+  return fn[!behind][bitdepth != 8];
+}
 struct fl_layout { size_t ticket, sao_done, final_done, pics, total; };
 fl_layout layout(int n, int w, int h)
 {
   const size_t ctus = (size_t)((w + 63) / 64) * ((h + 63) / 64), total = ctus * n;
   fl_layout L;
-  L.ticket = 0;
-  L.sao_done = 256;
+  uvgi_carver c;
+  L.ticket = c.take(256);
+  L.sao_done = c.take(2 * total * 4);          // one piece: the two flag arrays
   L.final_done = L.sao_done + total * 4;
-  L.pics = align_up(L.final_done + total * 4, 256);          // [0, pics): zeroed before every run
-  L.total = L.pics + (size_t)n * sizeof(fpic_dev);
+  L.pics = c.take((size_t)n * sizeof(fpic_dev));          // [0, pics): zeroed before every run
+  L.total = c.end;
   return L;
 }
 
@@ -109,19 +116,10 @@ int uvgi_filter_prepare(int bitdepth, const uvghip_ctu_params_t *params, const u
   std::vector<fpic_dev> pd(n_pictures);
   for (int i = 0; i < n_pictures; ++i) {
     const uvghip_ctu_picture_t &p = pictures[i];
-    const uvgi_pb_filter &f = filters[i];
-    if (!p.src_y || !p.src_u || !p.src_v || !p.rec_y || !p.rec_u || !p.rec_v || !p.cu || p.cu_stride < wc * 16 || p.src_stride < w || p.rec_stride < w ||
-        p.src_stride_c < w / 2 || p.rec_stride_c < w / 2)
-      return uvghip_set_error(hipErrorInvalidValue, "uvgi_filter_prepare: picture descriptor");
-    if (!f.dbk_y || !f.dbk_u || !f.dbk_v || !f.out_y || !f.out_u || !f.out_v || f.dbk_stride < w || f.dbk_stride_c < w / 2 || f.out_stride < w || f.out_stride_c < w / 2 ||
-        f.sao_type < 0 || f.sao_type > 3 || (f.sao_type && (!f.sao_info || !f.sao_models)))
-      return uvghip_set_error(hipErrorInvalidValue, "uvgi_filter_prepare: filter stage");
+    if (int rc = uvgi_check_picture(p, w, wc, false, "uvgi_filter_prepare: picture descriptor")) return rc;
+    if (int rc = uvgi_check_filter(filters[i], w, "uvgi_filter_prepare: filter stage")) return rc;
     fpic_dev &d = pd[i];
-    ctuf::filt_pic &g = d.F;
-    g.dbk_y = f.dbk_y; g.dbk_u = f.dbk_u; g.dbk_v = f.dbk_v; g.out_y = f.out_y; g.out_u = f.out_u; g.out_v = f.out_v;
-    g.dbk_stride = f.dbk_stride; g.dbk_stride_c = f.dbk_stride_c; g.out_stride = f.out_stride; g.out_stride_c = f.out_stride_c;
-    g.sao_info = f.sao_info; g.sao_models = f.sao_models; g.lambda = params->lambda; g.sao_type = f.sao_type; g.slice_type = slice_type; g.qp = params->qp;
-    g.is_b = slice_type == 0;
+    d.F = uvgi_filt_pic_of(filters[i], params->lambda, params->qp, slice_type);
     d.rec_y = p.rec_y; d.rec_u = p.rec_u; d.rec_v = p.rec_v; d.src_y = p.src_y; d.src_u = p.src_u; d.src_v = p.src_v; d.scu = p.cu;
     d.rec_stride = p.rec_stride; d.rec_stride_c = p.rec_stride_c; d.src_stride = p.src_stride; d.src_stride_c = p.src_stride_c; d.scu_stride = p.cu_stride; d.pad = 0;
   }
@@ -161,14 +159,8 @@ int uvgi_filter_run(int bitdepth, int n_pictures, int pic_w, int pic_h, void *wo
   A.final_done = reinterpret_cast<int32_t *>(ws + L.final_done);
   A.wc = (pic_w + 63) / 64; A.hc = (pic_h + 63) / 64; A.n_pictures = n_pictures; A.W = pic_w; A.H = pic_h;
   A.searched = searched;
-  const int total = A.wc * A.hc * n_pictures;
-  if (searched) {
-    const int grid = total < max_workgroups ? total : max_workgroups;
-    if (bitdepth == 8) hipLaunchKernelGGL((ctu_filter_kernel<uint8_t, true>), dim3(grid), dim3(256), sizeof(ctuf::filt_lds<uint8_t>), st, A);
-    else hipLaunchKernelGGL((ctu_filter_kernel<uint16_t, true>), dim3(grid), dim3(256), sizeof(ctuf::filt_lds<uint16_t>), st, A);
-  } else {
-    if (bitdepth == 8) hipLaunchKernelGGL((ctu_filter_kernel<uint8_t, false>), dim3(total), dim3(256), sizeof(ctuf::filt_lds<uint8_t>), st, A);
-    else hipLaunchKernelGGL((ctu_filter_kernel<uint16_t, false>), dim3(total), dim3(256), sizeof(ctuf::filt_lds<uint16_t>), st, A);
-  }
+  const int total = A.wc * A.hc * n_pictures, grid = searched && max_workgroups < total ? max_workgroups : total;
+  void *args[] = {&A};
+  (void)hipLaunchKernel(filter_kernel(bitdepth, searched != nullptr), dim3(grid), dim3(256), args, bitdepth == 8 ? sizeof(ctuf::filt_lds<uint8_t>) : sizeof(ctuf::filt_lds<uint16_t>), st);
   UVGHIP_CHECK_LAUNCH();
 }

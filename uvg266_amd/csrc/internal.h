@@ -9,6 +9,82 @@
 #include <vector>
 #include "../../include/uvg266_hip.h"
 
+int uvghip_set_error(hipError_t e, const char *where);          // context.hip
+
+// ---- what the device is assumed to hold (MI355X) and the launch caps that follow: constants, not hipDeviceProp -- the measurements
+// beside them were taken with these values ------------------------------------------------------------------------------------------------
+constexpr int uvgi_cus = 256, uvgi_lds_per_cu = 160 * 1024;          // 8 XCDs x 32 CUs; a CU's LDS
+// Search workgroups per CU: ctu_search_kernel's __launch_bounds__(256, 4) (four waves each, one per SIMD) and the one-wave P / B kernel,
+// whose registers allow one wave per SIMD.  A workgroup's LDS -- dynamic image plus the function-scope tables the build's .usage file
+// reports -- must fit this share: one more word and the device holds three workgroups per CU instead of four (-25 %).
+constexpr int uvgi_search_wgs_per_cu = 4, uvgi_search_lds_share = uvgi_lds_per_cu / uvgi_search_wgs_per_cu;
+constexpr int uvgi_wg_slots = uvgi_cus * uvgi_search_wgs_per_cu;          // search workgroups the device holds at once
+// Scratch slots of a search workspace: a workgroup claims one while it runs.  Twice what the device can hold of the kernel, so a free
+// bit always exists; small jobs take one slot per CTU, rounded up to whole bitmap words.
+constexpr int uvgi_max_slots = 2 * uvgi_wg_slots;
+// ctu_search_kernel's walkers-per-SIMD counters, indexed by what the hardware reports: [XCC_ID (3 bits)][HW_ID's SE, SH, CU (8 bits)][SIMD]
+constexpr int uvgi_simd_counters = 8 * 256 * 4;
+// uvghip_loop_plan_run_overlapped.  Beside a search that fills the device the stage's workgroups and the coder's waves displace search
+// workgroups (a CU's 160 KB of LDS are four search workgroups exactly: one coder wave of 10 KB costs the CU a whole one) and the group gets
+// SLOWER -- measured: 60 pictures of 1080p, up to 1020 CTUs in progress on 1024 slots, 543 -> 621 ms; 16 pictures 484 -> 415 ms, one
+// picture 461 -> 396 ms.  So: only while the pictures' wavefronts leave half the device free ...
+constexpr int uvgi_overlap_max_ctus = uvgi_wg_slots / 2;
+// ... and what runs beside the search is capped: a waiting filter workgroup or coder wave holds LDS a search workgroup cannot use.  The
+// filter stage gets an eighth of the slots, the coder a wave per CU.
+constexpr int uvgi_overlap_filter_cap = uvgi_wg_slots / 8, uvgi_overlap_coder_cap = uvgi_cus;
+// The in-flight P / B launch (uvgi_search_pb_inflight).  Its workgroups of three or four waves take a CU each, of one or two waves a
+// share of the slots.  A launch BESIDE it that it waits for (the I pictures' search, other_workgroups of four per CU) is left its CUs --
+// at most half the slots, so that the flight keeps half the device; a flight cut down to its room keeps a sixteenth of the CUs at least.
+constexpr int uvgi_flight_other_max = uvgi_wg_slots / 2, uvgi_flight_min_grid = uvgi_cus / 16;
+inline int uvgi_flight_grid_cap(int waves) { return waves >= 3 ? uvgi_cus : uvgi_wg_slots / waves; }
+inline int uvgi_flight_room(int other_workgroups) { return uvgi_cus - (other_workgroups + uvgi_search_wgs_per_cu - 1) / uvgi_search_wgs_per_cu; }
+static_assert(uvgi_search_lds_share == 40960 && uvgi_wg_slots == 1024 && uvgi_max_slots == 2048 && uvgi_simd_counters == 8192 && uvgi_overlap_max_ctus == 512 &&
+              uvgi_overlap_filter_cap == 128 && uvgi_overlap_coder_cap == 256 && uvgi_flight_other_max == 512 && uvgi_flight_min_grid == 16,
+              "the launch caps the goldens and the recorded timings were taken with");
+
+// ---- carving a workspace: offsets in the order they are taken, every one 256-byte aligned -----------------------------------------------
+constexpr size_t uvgi_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+struct uvgi_carver {
+  size_t at = 0, end = 0;          // the next offset; where the last piece really ends (a layout whose size is not rounded up)
+  size_t take(size_t bytes) { const size_t o = at; end = at + bytes; at = uvgi_align_up(end, 256); return o; }
+};
+// the slice data's tail of the three loop layouts (loop_plan.hip, loop_pb.hip): SAO decisions, the coder's table, the rows and their lengths
+struct uvgi_coder_tail {
+  size_t info, models, coder, row_bytes, rows;
+  int row_cap;          // twice the raw storage of a CTU row of 4:2:0 samples: no row of real content comes near
+  void carve_sao(uvgi_carver &c, size_t n, size_t ctus) { info = c.take(n * ctus * 34 * 4); models = c.take(n * ctus * 6 * 2); }
+  void carve_rows(uvgi_carver &c, int bitdepth, size_t n, int w, size_t hc, size_t coder_bytes)
+  {
+    row_cap = 3 * 64 * w * (bitdepth == 8 ? 1 : 2);
+    coder = c.take(coder_bytes); row_bytes = c.take(n * hc * 4); rows = c.take(n * hc * row_cap);
+  }
+};
+
+// ---- descriptor checks: one copy of every pointer and stride rule.  `text` is the caller's own error text, reported as it always was ------
+inline int uvgi_refuse_if(bool bad, const char *text) { return bad ? uvghip_set_error(hipErrorInvalidValue, text) : 0; }
+// params: the range every search takes.  depth_max_least: the all-intra kernel walks any pu-depth-intra range up to 4 (4 > depth_max is
+// tested, tests/test_ctu_emulation.py); the P / B search is only pinned against the reference with 4x4 intra leaves and asks for 4.
+inline int uvgi_check_params(const uvghip_ctu_params_t &p, int depth_max_least, bool needs_lambda_sqrt, const char *text)
+{
+  return uvgi_refuse_if(p.wpp != 1 || p.depth_min < 1 || p.depth_max < depth_max_least || p.depth_max > 4 || p.depth_min > p.depth_max || p.rough_levels < 2 ||
+                        p.rough_levels > 3 || p.qp < 0 || p.qp > 63 || p.qp_c < 0 || p.qp_c > 63 || !(p.lambda > 0) || (needs_lambda_sqrt && !(p.lambda_sqrt > 0)) ||
+                        p.rd < 0 || p.rd > 1, text);
+}
+// a searched picture of width w, wc CTUs a row (coeff / models: not for a caller that only filters it); text_strides: where the caller has
+// a text of its own for a stride smaller than the picture
+inline int uvgi_check_picture(const uvghip_ctu_picture_t &c, int w, int wc, bool needs_coeff_models, const char *text, const char *text_strides = nullptr)
+{
+  if (int rc = uvgi_refuse_if(!c.src_y || !c.src_u || !c.src_v || !c.rec_y || !c.rec_u || !c.rec_v || !c.cu || (needs_coeff_models && (!c.coeff || !c.models)) ||
+                              c.cu_stride < wc * 16, text)) return rc;
+  return uvgi_refuse_if(c.src_stride < w || c.rec_stride < w || c.src_stride_c < w / 2 || c.rec_stride_c < w / 2, text_strides ? text_strides : text);
+}
+template <typename OUT>          // uvghip_loop_picture_t / uvghip_loop_pb_picture_t: out_y .. out_stride_c
+inline int uvgi_check_out_planes(const OUT &q, int w, const char *text, const char *text_strides = nullptr)
+{
+  if (int rc = uvgi_refuse_if(!q.out_y || !q.out_u || !q.out_v, text)) return rc;
+  return uvgi_refuse_if(q.out_stride < w || q.out_stride_c < w / 2, text_strides ? text_strides : text);
+}
+
 // ---- ctu_search.hip: an all-intra search plan's run in two halves ------------------------------------------------------------------
 // For a caller that lets ANOTHER stream's kernel wait for this plan's per-CTU flags (pictures in flight behind an I picture,
 // uvghip_loop_pb_run_inflight_intra): reset -- the counters and flags back to zero, in stream order; the other stream waits for an event
@@ -31,6 +107,20 @@ struct uvgi_pb_filter {
   uint16_t *sao_models;
   int32_t sao_type, reserved;           // cfg.sao_type: 0 off, 1 edge, 2 band, 3 both
 };
+
+inline int uvgi_check_filter(const uvgi_pb_filter &f, int w, const char *text)
+{
+  return uvgi_refuse_if(!f.dbk_y || !f.dbk_u || !f.dbk_v || !f.out_y || !f.out_u || !f.out_v || f.dbk_stride < w || f.dbk_stride_c < w / 2 || f.out_stride < w ||
+                        f.out_stride_c < w / 2 || f.sao_type < 0 || f.sao_type > 3 || (f.sao_type && (!f.sao_info || !f.sao_models)), text);
+}
+// the stage of a w x h picture: deblocked into `dbk` (Y, U, V tightly packed), SAO into the caller's output planes, the decisions into the given arrays
+template <typename OUT>
+inline uvgi_pb_filter uvgi_pb_filter_of(const OUT &q, void *dbk, int bitdepth, int w, int h, int32_t *sao_info, uint16_t *sao_models, int sao_type)
+{
+  unsigned char *d = static_cast<unsigned char *>(dbk);
+  const size_t plane = (size_t)w * h * (bitdepth == 8 ? 1 : 2);
+  return uvgi_pb_filter{d, d + plane, d + plane + plane / 4, q.out_y, q.out_u, q.out_v, w, w / 2, q.out_stride, q.out_stride_c, sao_info, sao_models, sao_type, 0};
+}
 
 // ---- filters.hip: the filter stage as ONE launch over a group of searched pictures, a workgroup per CTU -------------------------------
 // What the all-intra loop plan runs behind its search instead of the chain of whole-picture kernels (snapshot deblocking, SAO statistics,

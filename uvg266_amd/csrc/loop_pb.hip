@@ -10,32 +10,44 @@
 
 namespace {
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+struct layout_t { size_t search, snap, rects_y, rects_c, edge[3], band[3], decide, params[3], total; uvgi_coder_tail tail; };
 
-struct layout_t { size_t search, snap, rects_y, rects_c, edge[3], band[3], decide, info, models, params[3], coder, row_bytes, rows, total; int row_cap; };
-
-layout_t layout_of(int bitdepth, int n, int w, int h)
+// inflight: the layout of uvghip_loop_pb_run_inflight (below) -- the filters run inside the search launch, so none of the chain's tables,
+// and `snap` holds the deblocked pictures
+layout_t layout_of(int bitdepth, int n, int w, int h, bool inflight = false)
 {
   const size_t ctus = (size_t)((w + 63) / 64) * ((h + 63) / 64), b = bitdepth == 8 ? 1 : 2;
   layout_t L;
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t o = at; at = align_up(at + bytes, 256); return o; };
-  L.search = take(uvghip_ctu_search_pb_workspace_bytes(n, w, h));
-  L.snap = take((size_t)n * ((size_t)w * h * 3 / 2) * b);
-  L.rects_y = take(ctus * sizeof(uvghip_rect_t));
-  L.rects_c = take(ctus * sizeof(uvghip_rect_t));
-  for (int c = 0; c < 3; ++c) { L.edge[c] = take((size_t)n * ctus * 40 * 4); L.band[c] = take((size_t)n * ctus * 64 * 4); }
-  L.decide = take(uvghip_sao_decide_workspace_bytes(n, w, h));
-  L.info = take((size_t)n * ctus * 34 * 4);
-  L.models = take((size_t)n * ctus * 6 * 2);
-  for (int c = 0; c < 3; ++c) L.params[c] = take((size_t)n * ctus * sizeof(uvghip_sao_param_t));
-  const size_t hc = (size_t)((h + 63) / 64);
-  L.row_cap = 3 * 64 * w * (int)b;
-  L.coder = take(uvghip_slice_rows_pb_workspace_bytes(n));
-  L.row_bytes = take((size_t)n * hc * 4);
-  L.rows = take((size_t)n * hc * L.row_cap);
-  L.total = at;
+  uvgi_carver c;
+  L.search = c.take(uvghip_ctu_search_pb_workspace_bytes(n, w, h));
+  L.snap = c.take((size_t)n * ((size_t)w * h * 3 / 2) * b);
+  if (!inflight) {
+    L.rects_y = c.take(ctus * sizeof(uvghip_rect_t));
+    L.rects_c = c.take(ctus * sizeof(uvghip_rect_t));
+    for (int k = 0; k < 3; ++k) { L.edge[k] = c.take((size_t)n * ctus * 40 * 4); L.band[k] = c.take((size_t)n * ctus * 64 * 4); }
+    L.decide = c.take(uvghip_sao_decide_workspace_bytes(n, w, h));
+  }
+  L.tail.carve_sao(c, n, ctus);
+  for (int k = 0; k < 3 && !inflight; ++k) L.params[k] = c.take((size_t)n * ctus * sizeof(uvghip_sao_param_t));
+  L.tail.carve_rows(c, bitdepth, n, w, (size_t)((h + 63) / 64), uvghip_slice_rows_pb_workspace_bytes(n));
+  L.total = c.at;
   return L;
+}
+
+// one body behind the two *_results entry points
+int results_of(int bitdepth, int n_pictures, int pic_w, int pic_h, bool inflight, void *workspace, const char *who, const int32_t **sao_info, const uint16_t **sao_models,
+               const uint8_t **rows, const int32_t **row_bytes, int *row_cap, int *n_rows)
+{
+  if ((bitdepth != 8 && bitdepth != 10) || n_pictures <= 0 || pic_w <= 0 || pic_h <= 0 || !workspace) return uvghip_set_error(hipErrorInvalidValue, who);
+  const uvgi_coder_tail t = layout_of(bitdepth, n_pictures, pic_w, pic_h, inflight).tail;
+  const unsigned char *ws = static_cast<const unsigned char *>(workspace);
+  if (sao_info) *sao_info = reinterpret_cast<const int32_t *>(ws + t.info);
+  if (sao_models) *sao_models = reinterpret_cast<const uint16_t *>(ws + t.models);
+  if (rows) *rows = ws + t.rows;
+  if (row_bytes) *row_bytes = reinterpret_cast<const int32_t *>(ws + t.row_bytes);
+  if (row_cap) *row_cap = t.row_cap;
+  if (n_rows) *n_rows = (pic_h + 63) / 64;
+  return 0;
 }
 
 }  // namespace
@@ -49,16 +61,7 @@ extern "C" size_t uvghip_loop_pb_workspace_bytes(int bitdepth, int n_pictures, i
 extern "C" int uvghip_loop_pb_results(int bitdepth, int n_pictures, int pic_w, int pic_h, void *workspace, const int32_t **sao_info, const uint16_t **sao_models,
                                       const uint8_t **rows, const int32_t **row_bytes, int *row_cap, int *n_rows)
 {
-  if ((bitdepth != 8 && bitdepth != 10) || n_pictures <= 0 || pic_w <= 0 || pic_h <= 0 || !workspace) return uvghip_set_error(hipErrorInvalidValue, __func__);
-  const layout_t L = layout_of(bitdepth, n_pictures, pic_w, pic_h);
-  unsigned char *ws = static_cast<unsigned char *>(workspace);
-  if (sao_info) *sao_info = reinterpret_cast<const int32_t *>(ws + L.info);
-  if (sao_models) *sao_models = reinterpret_cast<const uint16_t *>(ws + L.models);
-  if (rows) *rows = ws + L.rows;
-  if (row_bytes) *row_bytes = reinterpret_cast<const int32_t *>(ws + L.row_bytes);
-  if (row_cap) *row_cap = L.row_cap;
-  if (n_rows) *n_rows = (pic_h + 63) / 64;
-  return 0;
+  return results_of(bitdepth, n_pictures, pic_w, pic_h, false, workspace, __func__, sao_info, sao_models, rows, row_bytes, row_cap, n_rows);
 }
 
 extern "C" int uvghip_loop_pb_run(int bitdepth, const uvghip_loop_pb_picture_t *pictures, int n_pictures, int sao_type, void *workspace, void *stream)
@@ -71,9 +74,13 @@ extern "C" int uvghip_loop_pb_run(int bitdepth, const uvghip_loop_pb_picture_t *
   std::vector<uvghip_ctu_pb_picture_t> sp(n_pictures);
   for (int i = 0; i < n_pictures; ++i) {
     const uvghip_loop_pb_picture_t &q = pictures[i];
-    if (!q.out_y || !q.out_u || !q.out_v || q.out_stride < w || q.out_stride_c < w / 2) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run: output planes");
+    if (int rc = uvgi_check_out_planes(q, w, "uvghip_loop_pb_run: output planes")) return rc;
     // the filters run without a chroma QP table (deblock.hip: identity)
     if (q.search.params.qp_c != q.search.params.qp) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run: qp_c != qp needs a chroma QP table");
+    // The slice's context models start from frame_qp everywhere (uvg_init_contexts with state->frame->QP: the search, the coder); the SAO
+    // decision below takes ONE QP for its models and its CTUs.  A picture whose CTUs' QP differs from the frame's (per-CTU QP offsets) is not
+    // something this loop implements: refuse it instead of deciding SAO on other models than the coder's.
+    if (q.search.params.qp != q.search.frame_qp) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run: params.qp differs from frame_qp");
     sp[i] = q.search;
   }
   const layout_t L = layout_of(bitdepth, n_pictures, w, h);
@@ -101,8 +108,8 @@ extern "C" int uvghip_loop_pb_run(int bitdepth, const uvghip_loop_pb_picture_t *
     edge[c] = reinterpret_cast<int32_t *>(ws + L.edge[c]); band[c] = reinterpret_cast<int32_t *>(ws + L.band[c]);
     prm[c] = reinterpret_cast<uvghip_sao_param_t *>(ws + L.params[c]);
   }
-  int32_t *sao_info = reinterpret_cast<int32_t *>(ws + L.info), *row_bytes = reinterpret_cast<int32_t *>(ws + L.row_bytes);
-  uint16_t *sao_models = reinterpret_cast<uint16_t *>(ws + L.models);
+  int32_t *sao_info = reinterpret_cast<int32_t *>(ws + L.tail.info), *row_bytes = reinterpret_cast<int32_t *>(ws + L.tail.row_bytes);
+  uint16_t *sao_models = reinterpret_cast<uint16_t *>(ws + L.tail.models);
   const size_t snap_bytes = (size_t)w * h * 3 / 2 * b;
   // pictures that share QP, lambda and slice type (the same temporal position of several sequences) go through the SAO decision and
   // the coder together: runs of such pictures
@@ -113,10 +120,6 @@ extern "C" int uvghip_loop_pb_run(int bitdepth, const uvghip_loop_pb_picture_t *
            pictures[i1].search.slice_type == s0.slice_type && pictures[i1].search.frame_qp == s0.frame_qp)
       ++i1;
     const int m = i1 - i0, is_b = s0.slice_type == 0, qp = s0.params.qp;
-    // The slice's context models start from frame_qp everywhere (uvg_init_contexts with state->frame->QP: the search, the coder); the SAO
-    // decision below takes ONE QP for its models and its CTUs.  A picture whose CTUs' QP differs from the frame's (per-CTU QP offsets) is not
-    // something this loop implements: refuse it instead of deciding SAO on other models than the coder's.
-    if (s0.params.qp != s0.frame_qp) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run: params.qp differs from frame_qp");
     const size_t o0 = (size_t)i0 * ctus;
     if (sao_type) {
       for (int i = i0; i < i1; ++i) {
@@ -159,7 +162,7 @@ extern "C" int uvghip_loop_pb_run(int bitdepth, const uvghip_loop_pb_picture_t *
     // the slice data of the run's pictures: the search's hand-over and the SAO decisions through the arithmetic coder (its tables are
     // uploaded in stream order: a later run's upload comes after the earlier run's coder on the stream)
     if (int rc = uvghip_encode_slice_rows_pb(bitdepth, &s0.params, cp.data(), sl.data(), m, sao_type ? sao_info + o0 * 34 : nullptr, sao_type ? sao_models + o0 * 6 : nullptr,
-                                             ws + L.coder, ws + L.rows + (size_t)i0 * hc * L.row_cap, L.row_cap, row_bytes + (size_t)i0 * hc, stream))
+                                             ws + L.tail.coder, ws + L.tail.rows + (size_t)i0 * hc * L.tail.row_cap, L.tail.row_cap, row_bytes + (size_t)i0 * hc, stream))
       return rc;
     i0 = i1;
   }
@@ -168,46 +171,16 @@ extern "C" int uvghip_loop_pb_run(int bitdepth, const uvghip_loop_pb_picture_t *
 
 // ---- pictures in flight behind their references: one call = one persistent launch for the whole DAG (uvgi_search_pb_inflight: the
 // search with the per-CTU filters inside), then ONE coder launch over all pictures -- their QPs, lambdas and slice types may differ ----
-namespace {
-struct flight_t { size_t search, dbk, info, models, coder, row_bytes, rows, total; int row_cap; };
-flight_t flight_of(int bitdepth, int n, int w, int h)
-{
-  const size_t ctus = (size_t)((w + 63) / 64) * ((h + 63) / 64), b = bitdepth == 8 ? 1 : 2, hc = (size_t)((h + 63) / 64);
-  flight_t L;
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t o = at; at = align_up(at + bytes, 256); return o; };
-  L.search = take(uvghip_ctu_search_pb_workspace_bytes(n, w, h));
-  L.dbk = take((size_t)n * ((size_t)w * h * 3 / 2) * b);
-  L.info = take((size_t)n * ctus * 34 * 4);
-  L.models = take((size_t)n * ctus * 6 * 2);
-  L.row_cap = 3 * 64 * w * (int)b;
-  L.coder = take(uvghip_slice_rows_pb_workspace_bytes(n));
-  L.row_bytes = take((size_t)n * hc * 4);
-  L.rows = take((size_t)n * hc * L.row_cap);
-  L.total = at;
-  return L;
-}
-}  // namespace
-
 extern "C" size_t uvghip_loop_pb_inflight_workspace_bytes(int bitdepth, int n_pictures, int pic_w, int pic_h)
 {
   if ((bitdepth != 8 && bitdepth != 10) || n_pictures <= 0 || pic_w <= 0 || pic_h <= 0) return 0;
-  return flight_of(bitdepth, n_pictures, pic_w, pic_h).total;
+  return layout_of(bitdepth, n_pictures, pic_w, pic_h, true).total;
 }
 
 extern "C" int uvghip_loop_pb_inflight_results(int bitdepth, int n_pictures, int pic_w, int pic_h, void *workspace, const int32_t **sao_info, const uint16_t **sao_models,
                                                const uint8_t **rows, const int32_t **row_bytes, int *row_cap, int *n_rows)
 {
-  if ((bitdepth != 8 && bitdepth != 10) || n_pictures <= 0 || pic_w <= 0 || pic_h <= 0 || !workspace) return uvghip_set_error(hipErrorInvalidValue, __func__);
-  const flight_t L = flight_of(bitdepth, n_pictures, pic_w, pic_h);
-  unsigned char *ws = static_cast<unsigned char *>(workspace);
-  if (sao_info) *sao_info = reinterpret_cast<const int32_t *>(ws + L.info);
-  if (sao_models) *sao_models = reinterpret_cast<const uint16_t *>(ws + L.models);
-  if (rows) *rows = ws + L.rows;
-  if (row_bytes) *row_bytes = reinterpret_cast<const int32_t *>(ws + L.row_bytes);
-  if (row_cap) *row_cap = L.row_cap;
-  if (n_rows) *n_rows = (pic_h + 63) / 64;
-  return 0;
+  return results_of(bitdepth, n_pictures, pic_w, pic_h, true, workspace, __func__, sao_info, sao_models, rows, row_bytes, row_cap, n_rows);
 }
 
 namespace {
@@ -228,12 +201,12 @@ int run_flight(int bitdepth, const uvghip_loop_pb_picture_t *pictures, int n_pic
   if (!pictures || n_pictures <= 0 || !workspace || !ref_in_call || sao_type < 0 || sao_type > 3) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run_inflight");
   const int w = pictures[0].search.params.pic_w, h = pictures[0].search.params.pic_h;
   if (w <= 0 || h <= 0) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run_inflight");
-  const flight_t L = flight_of(bitdepth, n_pictures, w, h);
+  const layout_t L = layout_of(bitdepth, n_pictures, w, h, true);
   unsigned char *ws = static_cast<unsigned char *>(workspace);
   const int wc = (w + 63) / 64, hc = (h + 63) / 64, ctus = wc * hc;
-  const size_t b = bitdepth == 8 ? 1 : 2, plane = (size_t)w * h * b, planes = plane * 3 / 2;
-  int32_t *sao_info = reinterpret_cast<int32_t *>(ws + L.info), *row_bytes = reinterpret_cast<int32_t *>(ws + L.row_bytes);
-  uint16_t *sao_models = reinterpret_cast<uint16_t *>(ws + L.models);
+  const size_t planes = (size_t)w * h * (bitdepth == 8 ? 1 : 2) * 3 / 2;
+  int32_t *sao_info = reinterpret_cast<int32_t *>(ws + L.tail.info), *row_bytes = reinterpret_cast<int32_t *>(ws + L.tail.row_bytes);
+  uint16_t *sao_models = reinterpret_cast<uint16_t *>(ws + L.tail.models);
   std::vector<uvghip_ctu_pb_picture_t> sp(n_pictures);
   std::vector<uvgi_pb_filter> fl(n_pictures);
   std::vector<uvghip_ctu_picture_t> cp(n_pictures);
@@ -242,16 +215,11 @@ int run_flight(int bitdepth, const uvghip_loop_pb_picture_t *pictures, int n_pic
   for (int i = 0; i < n_pictures; ++i) {
     const uvghip_loop_pb_picture_t &q = pictures[i];
     const uvghip_ctu_pb_picture_t &s = q.search;
-    if (!q.out_y || !q.out_u || !q.out_v || q.out_stride < w || q.out_stride_c < w / 2) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run_inflight: output planes");
+    if (int rc = uvgi_check_out_planes(q, w, "uvghip_loop_pb_run_inflight: output planes")) return rc;
     sp[i] = s;
-    uvgi_pb_filter &f = fl[i];
-    unsigned char *d = ws + L.dbk + (size_t)i * planes;
-    f.dbk_y = d; f.dbk_u = d + plane; f.dbk_v = d + plane + plane / 4;
-    f.dbk_stride = w; f.dbk_stride_c = w / 2;
-    f.out_y = q.out_y; f.out_u = q.out_u; f.out_v = q.out_v; f.out_stride = q.out_stride; f.out_stride_c = q.out_stride_c;
-    f.sao_info = sao_info + (size_t)i * ctus * 34; f.sao_models = sao_models + (size_t)i * ctus * 6;
-    if (i < n_ext) { flags[i] = ext[i].searched_flags; f.sao_info = ext[i].sao_info; f.sao_models = ext[i].sao_models; }
-    f.sao_type = sao_type; f.reserved = 0;
+    if (i < n_ext) flags[i] = ext[i].searched_flags;
+    fl[i] = uvgi_pb_filter_of(q, ws + L.snap + (size_t)i * planes, bitdepth, w, h, i < n_ext ? ext[i].sao_info : sao_info + (size_t)i * ctus * 34,
+                              i < n_ext ? ext[i].sao_models : sao_models + (size_t)i * ctus * 6, sao_type);
     cp[i] = s.pic;
     if (i >= n_ext) sl[i] = uvgi_slice_pb_of(s);          // (the others are not coded here)
   }
@@ -261,8 +229,8 @@ int run_flight(int bitdepth, const uvghip_loop_pb_picture_t *pictures, int n_pic
   // the slice data of every picture it searched in one launch (a P / B picture's models start from its own frame_qp and slice type: `params`
   // only names the size); they keep their place in the results' arrays
   return uvghip_encode_slice_rows_pb(bitdepth, &pictures[n_ext].search.params, cp.data() + n_ext, sl.data() + n_ext, n_pictures - n_ext,
-                                     sao_type ? sao_info + (size_t)n_ext * ctus * 34 : nullptr, sao_type ? sao_models + (size_t)n_ext * ctus * 6 : nullptr, ws + L.coder,
-                                     ws + L.rows + (size_t)n_ext * hc * L.row_cap, L.row_cap, row_bytes + (size_t)n_ext * hc, stream);
+                                     sao_type ? sao_info + (size_t)n_ext * ctus * 34 : nullptr, sao_type ? sao_models + (size_t)n_ext * ctus * 6 : nullptr, ws + L.tail.coder,
+                                     ws + L.tail.rows + (size_t)n_ext * hc * L.tail.row_cap, L.tail.row_cap, row_bytes + (size_t)n_ext * hc, stream);
 }
 }  // namespace
 
@@ -296,7 +264,7 @@ extern "C" int uvghip_loop_pb_run_inflight_intra(int bitdepth, uvghip_loop_plan_
     other_workgroups += pl->n * (per < ctus ? per : ctus);
   }
   if (n_pictures < n_intra) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run_inflight_intra: fewer pictures than the plans hold");
-  if (other_workgroups > 512) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run_inflight_intra: the plans' launches need more than 512 workgroups");
+  if (other_workgroups > uvgi_flight_other_max) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run_inflight_intra: the plans' launches need more than 512 workgroups");
   for (int i = n_intra; i < n_pictures; ++i) {
     if (pictures[i].search.params.pic_w != w || pictures[i].search.params.pic_h != h)
       return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run_inflight_intra: a picture's size differs from the plans'");
@@ -327,7 +295,7 @@ extern "C" int uvghip_loop_pb_run_inflight_intra(int bitdepth, uvghip_loop_plan_
   UVGHIP_TRY(hipStreamWaitEvent(flight, p0->ev_fork, 0));
   // 2. the I pictures' "final" flags (which their coder waits for, behind the search on the I side) and the plans' "searched" flags to zero;
   //    the flight behind that: its kernel must not look at them before
-  const flight_t L = flight_of(bitdepth, n_pictures, w, h);
+  const layout_t L = layout_of(bitdepth, n_pictures, w, h, true);
   int32_t *final_flags = const_cast<int32_t *>(uvgi_search_pb_inflight_final_flags(n_pictures, w, h, static_cast<unsigned char *>(workspace) + L.search));
   UVGHIP_TRY(hipMemsetAsync(final_flags, 0, (size_t)n_intra * ctus * sizeof(int32_t), intra));
   for (int k = 0; k < n_plans; ++k)

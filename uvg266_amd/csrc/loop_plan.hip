@@ -10,29 +10,21 @@
 
 namespace {
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-struct layout_t { size_t search, snap, info, models, coder, row_bytes, rows, sums, filt, tick, total; int row_cap; };
+struct layout_t { size_t search, snap, sums, filt, tick, total; uvgi_coder_tail tail; };
 
 layout_t layout_of(int bitdepth, int n, int w, int h)
 {
-  const size_t ctus = (size_t)((w + 63) / 64) * ((h + 63) / 64), b = bitdepth == 8 ? 1 : 2;
   layout_t L;
-  size_t at = 0;
-  auto take = [&](size_t bytes) { const size_t o = at; at = align_up(at + bytes, 256); return o; };
-  L.search = take(uvghip_ctu_search_workspace_bytes(n, w, h));
-  L.snap = take((size_t)n * ((size_t)w * h * 3 / 2) * b);
-  L.info = take((size_t)n * ctus * 34 * 4);
-  L.models = take((size_t)n * ctus * 6 * 2);
+  uvgi_carver c;
+  L.search = c.take(uvghip_ctu_search_workspace_bytes(n, w, h));
+  L.snap = c.take((size_t)n * ((size_t)w * h * 3 / 2) * (bitdepth == 8 ? 1 : 2));
   const size_t hc = (size_t)((h + 63) / 64);
-  L.row_cap = 3 * 64 * w * (int)b;        // twice the raw storage of a CTU row of 4:2:0 samples: no row of real content comes near
-  L.coder = take(uvghip_slice_rows_workspace_bytes(n));
-  L.row_bytes = take((size_t)n * hc * 4);
-  L.rows = take((size_t)n * hc * L.row_cap);
-  L.sums = take((size_t)n * 3 * sizeof(uint32_t));
-  L.filt = take(uvgi_filter_workspace_bytes(n, w, h));
-  L.tick = take(256);
-  L.total = at;
+  L.tail.carve_sao(c, n, (size_t)((w + 63) / 64) * hc);
+  L.tail.carve_rows(c, bitdepth, n, w, hc, uvghip_slice_rows_workspace_bytes(n));
+  L.sums = c.take((size_t)n * 3 * sizeof(uint32_t));
+  L.filt = c.take(uvgi_filter_workspace_bytes(n, w, h));
+  L.tick = c.take(256);
+  L.total = c.at;
   return L;
 }
 
@@ -57,8 +49,7 @@ extern "C" int uvghip_loop_plan_create(int bitdepth, const uvghip_ctu_params_t *
   if (params->qp_c != params->qp) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_plan_create: qp_c != qp needs a chroma QP table, which the loop plan does not take");
   std::vector<uvghip_ctu_picture_t> sp(n_pictures);
   for (int i = 0; i < n_pictures; ++i) {
-    if (!pictures[i].out_y || !pictures[i].out_u || !pictures[i].out_v) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_plan_create: output planes");
-    if (pictures[i].out_stride < w || pictures[i].out_stride_c < w / 2) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_plan_create: output strides");
+    if (int rc = uvgi_check_out_planes(pictures[i], w, "uvghip_loop_plan_create: output planes", "uvghip_loop_plan_create: output strides")) return rc;
     sp[i] = pictures[i].search;
   }
   const layout_t L = layout_of(bitdepth, n_pictures, w, h);
@@ -71,12 +62,12 @@ extern "C" int uvghip_loop_plan_create(int bitdepth, const uvghip_ctu_params_t *
   pl->bitdepth = bitdepth; pl->n = n_pictures; pl->w = w; pl->h = h; pl->sao_type = sao_type;
   pl->ctus = wc * hc;
   pl->pics.assign(pictures, pictures + n_pictures);
-  pl->sao_info = reinterpret_cast<int32_t *>(ws + L.info);
-  pl->sao_models = reinterpret_cast<uint16_t *>(ws + L.models);
-  pl->coder_ws = ws + L.coder;
-  pl->rows = ws + L.rows;
-  pl->row_bytes = reinterpret_cast<int32_t *>(ws + L.row_bytes);
-  pl->row_cap = L.row_cap; pl->hc = hc;
+  pl->sao_info = reinterpret_cast<int32_t *>(ws + L.tail.info);
+  pl->sao_models = reinterpret_cast<uint16_t *>(ws + L.tail.models);
+  pl->coder_ws = ws + L.tail.coder;
+  pl->rows = ws + L.tail.rows;
+  pl->row_bytes = reinterpret_cast<int32_t *>(ws + L.tail.row_bytes);
+  pl->row_cap = L.tail.row_cap; pl->hc = hc;
   pl->sums = reinterpret_cast<uint32_t *>(ws + L.sums);
   pl->ctu_params = *params;
   pl->filt_ws = ws + L.filt;
@@ -85,15 +76,9 @@ extern "C" int uvghip_loop_plan_create(int bitdepth, const uvghip_ctu_params_t *
   // The in-loop filters are ONE launch behind the search, a workgroup per CTU (filters.hip, ctu_filter.h); the deblocked pictures go to
   // the workspace (per picture Y, U, V, tightly packed)
   std::vector<uvgi_pb_filter> fl(n_pictures);
-  const size_t plane = (size_t)w * h * (bitdepth == 8 ? 1 : 2);
-  for (int i = 0; i < n_pictures; ++i) {
-    uvgi_pb_filter &f = fl[i];
-    unsigned char *d = ws + L.snap + (size_t)i * (plane * 3 / 2);
-    f.dbk_y = d; f.dbk_u = d + plane; f.dbk_v = d + plane + plane / 4; f.dbk_stride = w; f.dbk_stride_c = w / 2;
-    f.out_y = pictures[i].out_y; f.out_u = pictures[i].out_u; f.out_v = pictures[i].out_v; f.out_stride = pictures[i].out_stride; f.out_stride_c = pictures[i].out_stride_c;
-    f.sao_info = pl->sao_info + (size_t)i * pl->ctus * 34; f.sao_models = pl->sao_models + (size_t)i * pl->ctus * 6;
-    f.sao_type = sao_type; f.reserved = 0;
-  }
+  const size_t planes = (size_t)w * h * (bitdepth == 8 ? 1 : 2) * 3 / 2;
+  for (int i = 0; i < n_pictures; ++i)
+    fl[i] = uvgi_pb_filter_of(pictures[i], ws + L.snap + (size_t)i * planes, bitdepth, w, h, pl->sao_info + (size_t)i * pl->ctus * 34, pl->sao_models + (size_t)i * pl->ctus * 6, sao_type);
   if (int rc = uvgi_filter_prepare(bitdepth, params, sp.data(), fl.data(), n_pictures, 2, pl->filt_ws)) { uvghip_ctu_plan_destroy(pl->search); delete pl; return rc; }
   *plan_out = pl;
   return 0;
@@ -123,16 +108,9 @@ extern "C" int uvghip_loop_plan_run_overlapped(uvghip_loop_plan_t *pl, void *str
 {
   UVGHIP_REQUIRE_READY();
   if (!pl) return uvghip_set_error(hipErrorInvalidValue, __func__);
-  // Beside a search that fills the device the stage's workgroups and the coder's waves displace search workgroups (a CU's 160 KB of LDS are four
-  // search workgroups exactly: one coder wave of 10 KB costs the CU a whole one) and the group gets SLOWER -- measured: 60 pictures of 1080p, up
-  // to 1020 CTUs in progress on 1024 slots, 543 -> 621 ms; 16 pictures 484 -> 415 ms, one picture 461 -> 396 ms.  So: only while the
-  // pictures' wavefronts leave half the device free.
-  const int overlap_max_ctus_in_progress = 512;
-  // what runs beside the search is capped: a waiting filter workgroup or coder wave holds LDS a search workgroup cannot use (a coder wave 10 KB
-  // of a CU's 160 KB beside four search workgroups of 40 KB: one wave costs the CU a search workgroup)
-  const int filter_cap = 128, coder_cap = 256;
+  // only while the pictures' wavefronts leave half the device free, and what runs beside the search capped (internal.h: the measurements)
   const int wc = (pl->w + 63) / 64, per = wc < pl->hc ? wc : pl->hc;
-  if ((long long)pl->n * per > overlap_max_ctus_in_progress) return uvghip_loop_plan_run(pl, stream);
+  if ((long long)pl->n * per > uvgi_overlap_max_ctus) return uvghip_loop_plan_run(pl, stream);
   hipStream_t st = uvghip_stream(stream);
   if (int rc = uvgi_loop_plan_side_streams(pl)) return rc;
   // all flags to zero in `stream`, the side streams behind that; then the search, so that it is in the queue before anything waits for it
@@ -144,10 +122,10 @@ extern "C" int uvghip_loop_plan_run_overlapped(uvghip_loop_plan_t *pl, void *str
   for (int i = 0; i < 2; ++i) UVGHIP_TRY(hipStreamWaitEvent(pl->side[i], pl->ev_fork, 0));
   // the filter stage: as many persistent workgroups as the pictures' wavefronts can have CTUs in progress, at most an eighth of the device
   long long g = (long long)per * pl->n;
-  if (g > filter_cap) g = filter_cap;
+  if (g > uvgi_overlap_filter_cap) g = uvgi_overlap_filter_cap;
   if (int rc = uvgi_filter_run(pl->bitdepth, pl->n, pl->w, pl->h, pl->filt_ws, uvgi_ctu_plan_done_flags(pl->search), (int)g, pl->side[0])) return rc;
   if (int rc = uvgi_encode_slice_rows_behind(pl->bitdepth, &pl->ctu_params, pl->n, pl->sao_info, pl->sao_models, uvgi_filter_final_flags(pl->n, pl->w, pl->h, pl->filt_ws),
-                                             pl->coder_ticket, coder_cap, pl->coder_ws, pl->rows, pl->row_cap, pl->row_bytes, pl->side[1]))
+                                             pl->coder_ticket, uvgi_overlap_coder_cap, pl->coder_ws, pl->rows, pl->row_cap, pl->row_bytes, pl->side[1]))
     return rc;
   for (int i = 0; i < 2; ++i) {
     UVGHIP_TRY(hipEventRecord(pl->ev_side[i], pl->side[i]));
@@ -323,8 +301,8 @@ extern "C" int uvghip_loop_plan_results(const uvghip_loop_plan_t *pl, const int3
 extern "C" size_t uvghip_loop_plan_alf_workspace_bytes(const uvghip_loop_plan_t *pl)
 {
   if (!pl) return 0;
-  return align_up(uvghip_alf_reconstruct_workspace_bytes(pl->w, pl->h), 256) + align_up(uvghip_slice_rows_alf_workspace_bytes(pl->n), 256) +
-         (size_t)pl->n * align_up((size_t)pl->ctus * 7 + (size_t)pl->ctus * sizeof(int16_t), 256);
+  return uvgi_align_up(uvghip_alf_reconstruct_workspace_bytes(pl->w, pl->h), 256) + uvgi_align_up(uvghip_slice_rows_alf_workspace_bytes(pl->n), 256) +
+         (size_t)pl->n * uvgi_align_up((size_t)pl->ctus * 7 + (size_t)pl->ctus * sizeof(int16_t), 256);
 }
 
 extern "C" int uvghip_loop_plan_alf_stage(uvghip_loop_plan_t *pl, uvghip_alf_decide_fn decide, void *user, int classification_shift, const uvghip_alf_planes_t *alf_out,
@@ -335,9 +313,9 @@ extern "C" int uvghip_loop_plan_alf_stage(uvghip_loop_plan_t *pl, uvghip_alf_dec
     return uvghip_set_error(hipErrorInvalidValue, __func__);
   hipStream_t st = uvghip_stream(stream);
   unsigned char *ws = static_cast<unsigned char *>(workspace);
-  unsigned char *ws_rec = ws, *ws_coder = ws_rec + align_up(uvghip_alf_reconstruct_workspace_bytes(pl->w, pl->h), 256);
-  unsigned char *ws_flags = ws_coder + align_up(uvghip_slice_rows_alf_workspace_bytes(pl->n), 256);
-  const size_t per = align_up((size_t)pl->ctus * 7 + (size_t)pl->ctus * sizeof(int16_t), 256), b = pl->bitdepth == 8 ? 1 : 2;
+  unsigned char *ws_rec = ws, *ws_coder = ws_rec + uvgi_align_up(uvghip_alf_reconstruct_workspace_bytes(pl->w, pl->h), 256);
+  unsigned char *ws_flags = ws_coder + uvgi_align_up(uvghip_slice_rows_alf_workspace_bytes(pl->n), 256);
+  const size_t per = uvgi_align_up((size_t)pl->ctus * 7 + (size_t)pl->ctus * sizeof(int16_t), 256), b = pl->bitdepth == 8 ? 1 : 2;
   std::vector<uvghip_slice_alf_t> sl(pl->n);
   std::vector<uvghip_ctu_picture_t> cp(pl->n);
   for (int i = 0; i < pl->n; ++i) {

@@ -885,11 +885,11 @@ slice_rows_kernel(const pic_dev *__restrict__ pics, const pb_dev *__restrict__ p
 extern "C" size_t uvghip_slice_rows_workspace_bytes(int n_pictures) { return n_pictures > 0 ? (size_t)n_pictures * sizeof(pic_dev) : 0; }
 extern "C" size_t uvghip_slice_rows_alf_workspace_bytes(int n_pictures)
 {
-  return n_pictures > 0 ? ((size_t)n_pictures * sizeof(pic_dev) + 255) / 256 * 256 + (size_t)n_pictures * sizeof(alf_dev) : 0;
+  return n_pictures > 0 ? uvgi_align_up((size_t)n_pictures * sizeof(pic_dev), 256) + (size_t)n_pictures * sizeof(alf_dev) : 0;
 }
 extern "C" size_t uvghip_slice_rows_pb_workspace_bytes(int n_pictures)
 {
-  return n_pictures > 0 ? ((size_t)n_pictures * sizeof(pic_dev) + 255) / 256 * 256 + (size_t)n_pictures * sizeof(pb_dev) : 0;
+  return n_pictures > 0 ? uvgi_align_up((size_t)n_pictures * sizeof(pic_dev), 256) + (size_t)n_pictures * sizeof(pb_dev) : 0;
 }
 
 int uvgi_slice_rows_prepare(const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, int n_pictures, void *workspace, bool ordered, hipStream_t st)
@@ -970,7 +970,7 @@ extern "C" int uvghip_encode_slice_rows_alf(int bitdepth, const uvghip_ctu_param
     for (int c = 0; c < 3; ++c) d.enabled[c] = q.enabled[c] != 0;
     for (int c = 0; c < 2; ++c) { d.cc_enabled[c] = q.cc_enabled[c] != 0; d.cc_count[c] = q.cc_filter_count[c]; }
   }
-  unsigned char *aw = static_cast<unsigned char *>(workspace) + ((size_t)n_pictures * sizeof(pic_dev) + 255) / 256 * 256;
+  unsigned char *aw = static_cast<unsigned char *>(workspace) + uvgi_align_up((size_t)n_pictures * sizeof(pic_dev), 256);
   if (int rc = uvghip_upload_ordered(aw, ad.data(), ad.size() * sizeof(alf_dev), st)) return rc;
   slice_rows_kernel<false><<<n_pictures * hc, 64, 0, st>>>(static_cast<const pic_dev *>(workspace), nullptr, sao_info, sao_models, W, H, params->qp, bitdepth, out, row_cap, row_bytes,
                                                     reinterpret_cast<const alf_dev *>(aw));
@@ -1000,7 +1000,7 @@ extern "C" int uvghip_encode_slice_rows_pb(int bitdepth, const uvghip_ctu_params
     memcpy(d.ref_pocs, q.ref_pocs, sizeof d.ref_pocs); memcpy(d.l_size, q.l_size, sizeof d.l_size); memcpy(d.l, q.l, sizeof d.l);
     d.col = q.col; d.inter4 = q.inter4; d.models_inter = q.models_inter; d.col_stride = q.col_stride; d.pad = 0;
   }
-  unsigned char *pbw = static_cast<unsigned char *>(workspace) + ((size_t)n_pictures * sizeof(pic_dev) + 255) / 256 * 256;
+  unsigned char *pbw = static_cast<unsigned char *>(workspace) + uvgi_align_up((size_t)n_pictures * sizeof(pic_dev), 256);
   if (int rc = uvghip_upload_ordered(pbw, pd.data(), pd.size() * sizeof(pb_dev), st)) return rc;
   slice_rows_kernel<false><<<n_pictures * hc, 64, sizeof(row_state_pb), st>>>(static_cast<const pic_dev *>(workspace), reinterpret_cast<const pb_dev *>(pbw), sao_info, sao_models,
                                                                        W, H, params->qp, bitdepth, out, row_cap, row_bytes);

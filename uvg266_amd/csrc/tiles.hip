@@ -49,7 +49,6 @@ struct uvghip_tiles_plan {
 
 namespace {
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // the grid from the columns' widths and the rows' heights in CTUs (encoder->tiles_col_width / tiles_row_height)
 int grid_of(int pic_w, int pic_h, const std::vector<int> &colw, const std::vector<int> &rowh, std::vector<uvghip_rect_t> &tiles, std::vector<int> &first_ctu)
@@ -224,9 +223,10 @@ extern "C" size_t uvghip_tiles_workspace_bytes_split(int bitdepth, int n_picture
   std::vector<class_key> keys;
   classes_of(t, owned, keys, cls_of, slot_of);
   if (keys.empty()) return 0;
-  size_t at = align_up((size_t)n_pictures * 3 * sizeof(uint32_t), 256);
-  for (const class_key &k : keys) at += align_up(uvghip_loop_workspace_bytes(bitdepth, n_pictures * k.count, k.w, k.h), 256);
-  return at;
+  uvgi_carver c;
+  c.take((size_t)n_pictures * 3 * sizeof(uint32_t));
+  for (const class_key &k : keys) c.take(uvghip_loop_workspace_bytes(bitdepth, n_pictures * k.count, k.w, k.h));
+  return c.at;
 }
 
 // pictures: the WHOLE pictures (planes with their strides; cu with cu_stride >= 16 * CTUs per picture row); coeff / models hold the CTUs in
@@ -271,10 +271,10 @@ extern "C" int uvghip_tiles_plan_create_split(int bitdepth, const uvghip_ctu_par
   }
   const int wc = (pl->w + 63) / 64;
   for (int i = 0; i < n_pictures; ++i) {
-    const uvghip_ctu_picture_t &s = pictures[i].search;
-    if (!s.src_y || !s.src_u || !s.src_v || !s.rec_y || !s.rec_u || !s.rec_v || !s.cu || !s.coeff || !s.models || !pictures[i].out_y || !pictures[i].out_u || !pictures[i].out_v ||
-        s.src_stride < pl->w || s.rec_stride < pl->w || s.src_stride_c < pl->w / 2 || s.rec_stride_c < pl->w / 2 || s.cu_stride < wc * 16 || pictures[i].out_stride < pl->w ||
-        pictures[i].out_stride_c < pl->w / 2) { delete pl; return uvghip_set_error(hipErrorInvalidValue, "uvghip_tiles_plan_create: a picture's planes, tables or strides"); }
+    const char *const what = "uvghip_tiles_plan_create: a picture's planes, tables or strides";
+    int rc = uvgi_check_picture(pictures[i].search, pl->w, wc, true, what);
+    if (!rc) rc = uvgi_check_out_planes(pictures[i], pl->w, what);
+    if (rc) { delete pl; return rc; }
   }
   pl->pics.assign(pictures, pictures + n_pictures);
   std::vector<class_key> keys;
@@ -288,7 +288,8 @@ extern "C" int uvghip_tiles_plan_create_split(int bitdepth, const uvghip_ctu_par
   for (size_t t = 0; t < pl->tiles.size(); ++t) if (pl->owned[t]) pl->classes[pl->cls_of[t]].ids.push_back((int)t);
   unsigned char *ws = static_cast<unsigned char *>(workspace);
   pl->sums = reinterpret_cast<uint32_t *>(ws);
-  size_t at = align_up((size_t)n_pictures * 3 * sizeof(uint32_t), 256);
+  uvgi_carver carve;
+  carve.take((size_t)n_pictures * 3 * sizeof(uint32_t));          // pl->sums
   const size_t b = bitdepth == 8 ? 1 : 2;
   for (auto &c : pl->classes) {
     const int per = (int)c.ids.size();
@@ -310,8 +311,8 @@ extern "C" int uvghip_tiles_plan_create_split(int bitdepth, const uvghip_ctu_par
       }
     uvghip_ctu_params_t p = *params;
     p.pic_w = c.w; p.pic_h = c.h;
-    if (int rc = uvghip_loop_plan_create(bitdepth, &p, sub.data(), n_pictures * per, sao_type, ws + at, &c.plan)) { destroy(pl); return rc; }
-    at += align_up(uvghip_loop_workspace_bytes(bitdepth, n_pictures * per, c.w, c.h), 256);
+    unsigned char *const class_ws = ws + carve.take(uvghip_loop_workspace_bytes(bitdepth, n_pictures * per, c.w, c.h));
+    if (int rc = uvghip_loop_plan_create(bitdepth, &p, sub.data(), n_pictures * per, sao_type, class_ws, &c.plan)) { destroy(pl); return rc; }
     hipError_t e = hipStreamCreateWithFlags(&c.st, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c.done, hipEventDisableTiming);
     if (e != hipSuccess) { destroy(pl); return uvghip_set_error(e, "uvghip_tiles_plan_create: streams"); }
