@@ -36,10 +36,38 @@
 #include "inter_cand_dev.h"
 #endif
 
+// ---- build configurations ------------------------------------------------------------------------------------------------------
+// Two things select what this header, ctu_leaf4.h and ctu_pb.h compile to: the compiler (hipcc defines __HIPCC__: the device build;
+// g++: the host emulation, one lane) and CTU_PB (the kernel of P / B pictures, ctu_pb.h).  What is really built:
+//
+//   configuration       translation units                                    built by
+//   device, intra       ctu_search.hip, slice_coder.hip                      csrc/Makefile
+//   device, CTU_PB      ctu_search_pb.hip (defines CTU_PB before including)  csrc/Makefile
+//   host, intra         tests/emul/ctu_emul.cpp                              tests/emul/Makefile
+//   host, CTU_PB        tests/emul/ctu_pb_emul.cpp (-DCTU_PB)                tests/emul/Makefile
+//   ... each device build again with EXTRA=-DCTU_PROFILE (a library of its own for tools/dev/*, see tools/dev/README.md), and
+//   ctu_search.hip / ctu_search_pb.hip with EXTRA=-DCTU_POISON_LDS=0xA5 (a debug build: the launch fills the LDS image first)
+//
+//   switch        what it changes
+//   __HIPCC__     64 lanes and wave fences instead of one lane (the macros below); the 4x4 leaf on ctu_leaf4.h (lds::lf_*, eval_cu4,
+//                 coder_area4, a 4x4 arena share without the rough search's and RDOQ's arrays) -- the host keeps eval_cu for it;
+//                 its own rdoq_wave (the host's: ctu_rdoq_emul.h) and rough_costs; the depth waves' mailboxes instead of calls in
+//                 place; the slim images: lds_cfg<uint16_t>::slim of the intra kernel (cand_px, the 32x32 arena share and the two
+//                 large scans in the workgroup's global scratch), lds_cfg<PX>::slim_scan with CTU_PB (the scans only)
+//   CTU_PB        NMX = 257 + 18 models per set; level_state::mot / fl / cbf4; wctx::rq_root; lds::pb .. cur64 (the inter state, the
+//                 leaf and depth waves' own) in place of lds::req64 .. h64 (the 64x64 candidate beside the walk, the coder's pass
+//                 by model); one arena region for the depths 1..3; scratch::save_mot .. prof_pb; job::pb .. init_qp; the extra
+//                 parameter of eval_cu (forced_mode) and of recon_tu / recon_tu_inl (flags); no chroma helper
+//   CTU_PROFILE   lds::prof_w in front of the image; on the device the timer macros below count s_memtime ticks into
+//                 scratch::prof / prof_lf / prof_pb (always there; read by slot number by tools/dev/*) -- with CTU_PROFILE_WALK the
+//                 P / B phases of the walk's wave only
+// Every macro that depends on these is defined here and nowhere else.
 #if defined(__HIPCC__)
 #define CTU_NOINLINE __attribute__((noinline))
+#define CTU_INLINE __attribute__((always_inline))
 #define CTU_INLINE1 __attribute__((always_inline))          // one call site: no call, no callee-saved registers through the stack
 #define CTU_DEV static __device__
+#define CTU_SHARED __shared__
 // Everything the search computes is WAVE-local: a depth of the quad tree is worked by one wave (see search_ctu), so "all lanes"
 // means the 64 lanes of that wave and a hand-over between regions is a wave-level fence, not a workgroup barrier.
 #define CTU_TID ((int)(threadIdx.x & 63))
@@ -55,10 +83,16 @@
 #define BLK_TID ((int)threadIdx.x)
 #define BLK_NT ((int)blockDim.x)
 #define BLK_SYNC() __syncthreads()
+// a load that must see what another wave of this workgroup stored to global memory earlier (served by L2, not by this CU's L1)
+#define CTU_GLOAD(p) __builtin_nontemporal_load(p)
+#define CTU_LDS __attribute__((address_space(3)))
+#define CTU_GLB __attribute__((address_space(1)))
 #else
 #define CTU_NOINLINE
+#define CTU_INLINE
 #define CTU_INLINE1
 #define CTU_DEV static inline
+#define CTU_SHARED static
 #define CTU_TID 0
 #define CTU_NT 1
 #define CTU_WAVE (ctu::g_emul_wave)
@@ -66,36 +100,57 @@
 #define BLK_TID 0
 #define BLK_NT 1
 #define BLK_SYNC() ((void)0)
-#endif
-// a load that must see what another wave of this workgroup stored to global memory earlier (served by L2, not by this CU's L1)
-#if defined(__HIPCC__)
-#define CTU_GLOAD(p) __builtin_nontemporal_load(p)
-#define CTU_LDS __attribute__((address_space(3)))
-#define CTU_GLB __attribute__((address_space(1)))
-#else
 #define CTU_GLOAD(p) (*(p))
 #define CTU_LDS
 #define CTU_GLB
 #endif
-// optional phase timers (lane 0 of the wave, s_memtime ticks) -- compiled in with -DCTU_PROFILE, results in scratch::prof[wave]
+// RDOQ prices a luma block's "no coefficients" with the root cbf when the block belongs to an inter CU (wctx::rq_root)
+#if defined(CTU_PB)
+#define CTU_RQ_ROOT(V) ((V)->rq_root)
+#else
+#define CTU_RQ_ROOT(V) 0
+#endif
+// The phase timers of a CTU_PROFILE device build: lane 0 of the wave, s_memtime ticks.  No function body tests the switch itself.
+//   CTU_T0 / CTU_T1(W, slot)   a bracketed phase into scratch::prof[wave][slot]; PB_T0 / PB_T1: into scratch::prof_pb[slot]
+//   RQ_T0(W) ... RQ_T(slot)    consecutive phases of one function, each ending at its mark, into scratch::prof[wave][slot]
+//   LF_T0() ... LF_T(slot)     the same for the 4x4 leaf on the walk's wave, into scratch::prof_lf[slot] (`J` in scope)
+//   CTU_HELPED / CTU_TW0 / CTU_TW1, PB_COUNT, CTU_PROF_RESET / PB_PROF_RESET: the counters and the reset that are not a phase
+// RQ_T0 and the last group stand as statements WITHOUT a semicolon of their own: a build without the switch has no token there.
 #if defined(__HIPCC__) && defined(CTU_PROFILE)
 #define CTU_T0() const unsigned long long ctu_t0__ = __builtin_amdgcn_s_memtime()
 #define CTU_T1(W, slot) do { if (CTU_TID == 0) (W)->prof[CTU_WAVE][slot] += __builtin_amdgcn_s_memtime() - ctu_t0__; } while (0)
+#define RQ_T0(W) scratch *const rq_w__ = (W); unsigned long long tq = __builtin_amdgcn_s_memtime();
+#define RQ_T(slot) do { const unsigned long long t2 = __builtin_amdgcn_s_memtime(); if (CTU_TID == 0) rq_w__->prof[CTU_WAVE][slot] += t2 - tq; tq = t2; } while (0)
+#define LF_T0() unsigned long long tq = __builtin_amdgcn_s_memtime()
+#define LF_T(slot) do { const unsigned long long t2 = __builtin_amdgcn_s_memtime(); if (CTU_TID == 0 && CTU_WAVE == 0) J.W->prof_lf[slot] += t2 - tq; tq = t2; } while (0)
+// the chroma helper (help_post) on depth 3's counters: Cb blocks it took (slot 19) / the walk kept (20), the walk's wait for it (21)
+#define CTU_HELPED(W, on, helped) if (on) { SERIAL (W)->prof[1][(helped) ? 19 : 20] += 1; }
+#define CTU_TW0() const unsigned long long tw = __builtin_amdgcn_s_memtime();
+#define CTU_TW1(W) SERIAL (W)->prof[1][21] += __builtin_amdgcn_s_memtime() - tw;
+#define CTU_PROF_RESET(S, J) BLK_FOR(i, 4 * 32) (J).W->prof[i >> 5][i & 31] = 0; BLK_FOR(i, 16) (J).W->prof_lf[i] = 0; (S)->prof_w = (J).W;
+#define PB_T0() const unsigned long long pb_t0__ = __builtin_amdgcn_s_memtime()
+#if defined(CTU_PROFILE_WALK)      // only the walk's wave counts the phases of eval_pb (slots < 14): they add up to its time
+#define PB_T1(W, slot) do { if (CTU_TID == 0 && ((slot) >= 14 || CTU_WAVE == 0)) (W)->prof_pb[slot] += __builtin_amdgcn_s_memtime() - pb_t0__; } while (0)
+#else
+#define PB_T1(W, slot) do { if (CTU_TID == 0) (W)->prof_pb[slot] += __builtin_amdgcn_s_memtime() - pb_t0__; } while (0)
+#endif
+#define PB_COUNT(W, slot) SERIAL (W)->prof_pb[slot] += 1;
+#define PB_PROF_RESET(S, J) BLK_FOR(i, 24) (J).W->prof_pb[i] = 0; BLK_FOR(i, 4 * 32) (J).W->prof[i >> 5][i & 31] = 0; (S)->prof_w = (J).W;
 #else
 #define CTU_T0() ((void)0)
 #define CTU_T1(W, slot) ((void)0)
-#endif
-#if defined(__HIPCC__) && defined(CTU_PROFILE)
-#define RQ_T(slot) do { const unsigned long long t2 = __builtin_amdgcn_s_memtime(); if (CTU_TID == 0) W->prof[CTU_WAVE][slot] += t2 - tq; tq = t2; } while (0)
-#else
+#define RQ_T0(W)
 #define RQ_T(slot) ((void)0)
-#endif
-#if defined(__HIPCC__) && defined(CTU_PROFILE)
-#define LF_T(slot) do { const unsigned long long t2 = __builtin_amdgcn_s_memtime(); if (CTU_TID == 0 && CTU_WAVE == 0) J.W->prof_lf[slot] += t2 - tq; tq = t2; } while (0)
-#define LF_T0() unsigned long long tq = __builtin_amdgcn_s_memtime()
-#else
-#define LF_T(slot) ((void)0)
 #define LF_T0() ((void)0)
+#define LF_T(slot) ((void)0)
+#define CTU_HELPED(W, on, helped)
+#define CTU_TW0()
+#define CTU_TW1(W)
+#define CTU_PROF_RESET(S, J)
+#define PB_T0() ((void)0)
+#define PB_T1(W, slot) ((void)0)
+#define PB_COUNT(W, slot)
+#define PB_PROF_RESET(S, J)
 #endif
 #define LDSP(T, p) ((CTU_LDS T *)(p))          // a pointer known to point into the workgroup's LDS image (device: ds_* instead of flat_*)
 // ... and one that points into the LDS image OR, in a slim build (lds_cfg below), into the workgroup's global scratch: a generic pointer
@@ -104,20 +159,6 @@
 #define PAR_FOR(i, n) for (int i = CTU_TID; i < (n); i += CTU_NT)
 #define BLK_FOR(i, n) for (int i = BLK_TID; i < (n); i += BLK_NT)
 #define SERIAL if (CTU_TID == 0)
-#define LANE0 if (CTU_TID == 0)
-#define WFOR(i, n) PAR_FOR(i, n)
-#define WSYNC() CTU_SYNC()
-
-// the 4x4 leaves of an I picture's CTU go through the register-resident formulation of ctu_leaf4.h (device builds; -DCTU_LEAF_OLD keeps
-// the general CU evaluation for them: the A/B build of tools/dev)
-#if defined(__HIPCC__) && !defined(CTU_LEAF_OLD)
-#define CTU_LEAF4 1
-#endif
-// ... what the I-picture kernel builds on top of it (the 8x8 CU's chroma blocks and the 64x64 candidate's chroma on other waves, the
-// coder pass by 8x8 areas, the slim 10-bit image); the P / B kernel (ctu_pb.h) takes the 4x4 CU itself and the 4x4 bit count
-#if defined(CTU_LEAF4) && !defined(CTU_PB)
-#define CTU_LEAF4X 1
-#endif
 
 namespace ctu {
 
@@ -170,12 +211,12 @@ struct level_state {        // search_cu's locals, per depth
 // candidate touch: the depth-1 candidate's samples, the depth-1 scratch's levels, the 16x16 / 32x32 coefficient scans -- they live in
 // the workgroup's global scratch (L1 / L2 resident) behind generic pointers.  8-bit, P / B and host builds are not slim.
 // (slim_scan alone: only the two large scans move -- the P / B kernel, whose image also carries the inter state)
-#if defined(CTU_PB) && defined(__HIPCC__) && !defined(CTU_NO_SLIM)
+#if !defined(__HIPCC__)
+template <typename PX> struct lds_cfg { enum { slim = 0, slim_scan = 0 }; };
+#elif defined(CTU_PB)
 template <typename PX> struct lds_cfg { enum { slim = 0, slim_scan = 1 }; };
 #else
 template <typename PX> struct lds_cfg { enum { slim = 0, slim_scan = 0 }; };
-#endif
-#if defined(CTU_LEAF4X) && !defined(CTU_NO_SLIM)
 template <> struct lds_cfg<uint16_t> { enum { slim = 1, slim_scan = 1 }; };
 #endif
 template <typename PX, typename T, bool SLIM = (lds_cfg<PX>::slim != 0)> struct mg_ptr { typedef CTU_LDS T *type; };
@@ -212,18 +253,13 @@ struct wctx {
   int32_t rq_root;                                  // RDOQ prices a luma block's "no coefficients" with the root cbf (a block of an inter CU, rdo.c:1774)
 #endif
 };
-#if defined(CTU_PB)
-#define CTU_RQ_ROOT(V) ((V)->rq_root)
-#else
-#define CTU_RQ_ROOT(V) 0
-#endif
 
 constexpr int arena_bytes(int n, bool slim = false)     // one depth's share of the arena (n = its luma block size)
 {
   if (slim && n == 32) return (4 * (4 * n + 8) * 2 + 2 * n * n * 2 + 15) & ~15;      // (the levels live in scratch::lv32)
   // reference rows, two transform buffers, levels (y, u, v), [4x4 only: the rough search's partial costs -- larger blocks keep
   // them in the transform buffers, idle during the rough search], [<= 8x8: RDOQ's two per-position cost arrays]
-#if defined(CTU_LEAF4)
+#if defined(__HIPCC__)
   // (the 4x4 leaf keeps the rough search's costs and RDOQ's per-position costs in registers: reference rows, transform buffers, levels only)
   if (n == 4) return (4 * (4 * n + 8) * 2 + 2 * n * n * 2 + (n * n + 2 * 16) * 2 + 15) & ~15;
 #endif
@@ -304,7 +340,7 @@ template <typename PX> struct lds {
   int32_t rot;                                      // index of the wave with role 0 (CTU_WAVE)
   int32_t req[4], done[4];                          // depth pipeline: evaluation requests / completions per depth
   int32_t hreq, hdone, help[6];                     // the chroma helper (help_post): requests / completions; area x, y, mode -> has_coeffs, SSD
-#if defined(CTU_LEAF4)
+#if defined(__HIPCC__)
   // ctu_leaf4.h: the cubic interpolation filter (4 x int8 per phase), intraPredAngle | invAngle << 8 per |mode distance|, per raster
   // position of a 4x4 block (positions later in scan order | scan index << 16 | raster of the next scan index << 20), the 8x8 area
   // whose source samples are parked in lf_src ([0, 64) luma, [64, 80) Cb, [80, 96) Cr)
@@ -376,8 +412,6 @@ struct scratch {
   uint8_t save_fl[256][8];
   int32_t pb_mot[17 * 17 + 1][8];  // pb_state::mot / fl (icand::unit is eight int32)
   uint8_t pb_fl[17 * 17][8];
-#endif
-#if defined(CTU_PB)
   unsigned long long prof_pb[24];     // CTU_PROFILE, ctu_pb.h: cycles of the phases of the P / B walk (lane 0 of the wave); 16.. : waits of the walk, the other waves' busy time
 #endif
   unsigned long long prof_lf[16];     // CTU_PROFILE, ctu_leaf4.h: cycles of the 4x4 leaf's steps (the walk's wave)
@@ -422,11 +456,6 @@ template <typename PX> CTU_DEV CTU_GLB const PX *src_block(const job<PX> &J, int
 // Tables every serial walk reads per bin live in LDS (a lone lane pays the full latency of every load: out of device memory the
 // entropy table alone cost most of the search's time): the 512 bit costs, the models' window bytes, and the bit costs of the
 // models uvg_rdoq prices with (fixed for the CTU).  Function-scope LDS, filled by load_ctu.
-#if defined(__HIPCC__)
-#define CTU_SHARED __shared__
-#else
-#define CTU_SHARED static
-#endif
 CTU_DEV uint32_t *tab_ebits() { CTU_SHARED uint32_t t[512]; return t; }
 CTU_DEV uint8_t *tab_rate() { CTU_SHARED uint8_t t[(NMX + 7) & ~7]; return t; }
 CTU_DEV uint32_t *tab_rdoq_bits() { CTU_SHARED uint32_t t[2 * 244]; return t; }
@@ -823,10 +852,7 @@ template <typename PX> CTU_INLINE1 CTU_DEV void search_intra_rough(lds<PX> *S, c
   wctx *const V = wv_of(S);
   const params &P = J.P;
   const int T = n >= 8 ? 8 : 4, tiles = (n / T) * (n / T);
-#if defined(__HIPCC__) && defined(CTU_PROFILE)
-  scratch *const W = J.W;
-  unsigned long long tq = __builtin_amdgcn_s_memtime();
-#endif
+  RQ_T0(J.W)
   SERIAL {
     const cu4 *l, *a;
     mpm_neighbours(S, x, y, lx, ly, n, &l, &a);
@@ -1284,11 +1310,6 @@ CTU_NOINLINE CTU_DEV int rdoq_serial(const uint8_t *st, const uint16_t *scan, sc
 // regular: regular bins remain (reg_bins >= 4), go_rice is then the value carried from the position coded before; otherwise the
 // position is priced as bypass-coded and its Rice parameter comes from the levels decided around it.
 struct rdoq_pos { int level; double cc, cs; };
-#if defined(__HIPCC__)
-#define CTU_INLINE __attribute__((always_inline))
-#else
-#define CTU_INLINE
-#endif
 template <typename DP> CTU_INLINE CTU_DEV rdoq_pos rdoq_decide_inl(const rdoq_env &E, CTU_LDS const int16_t *coef, DP dst, int n, int l2, int color, int blkpos, bool is_last,
                              bool regular, int go_rice, double c0, int *mal_out)
 {
@@ -1318,297 +1339,7 @@ template <typename DP> CTU_NOINLINE CTU_DEV rdoq_pos rdoq_decide(const rdoq_env 
 }
 
 #if !defined(__HIPCC__)
-// uvg_rdoq (rdo.c:1449-1870) by the first wave: same arithmetic as rdoq_serial, restructured around what is sequential in it.
-//   * every position's quantisation candidates and its level-0 cost: all positions at once;
-//   * a level decision reads only levels decided on later anti-diagonals (the context template looks right / down), so the <= 4
-//     positions of one anti-diagonal of a 4x4 group are decided together, 7 steps per group -- as long as the regular-bin budget
-//     cannot run out inside the group (an upper bound from the candidates says so) or has run out for good; the one or two groups
-//     where it does run out are walked position by position;
-//   * the double-precision sums the reference forms in scan order (base cost, group statistics) and the group decision that
-//     compares them: lane 0, from the group's staged costs; the final cbf / last-position search: lane 0.
-// Result: V->rq_i[1] = whether any level survived; levels in dst.
-template <typename PX> CTU_NOINLINE CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W, const int16_t *coef_, int16_t *dst_, int n, int color, int cbf_u, int qp_scaled,
-                                              double lambda, int bitdepth)
-{
-  wctx *const V = wv_of(S);
-  CTU_LDS const int16_t *const coef = LDSP(const int16_t, coef_);
-  typename mg_ptr<PX, int16_t>::type const dst = MGP(PX, int16_t, dst_);
-  const int l2 = ilog2_dev(n), nn = n * n, cgw = n >> 2;
-  const uint16_t *scan = scan_of(S, l2);
-  rdoq_env E;
-  E.st = S->rdoq_state; E.t = color ? 1 : 0; E.lambda = lambda;
-  const int transform_shift = 15 - bitdepth - l2;
-  E.q_bits = 14 + qp_scaled / 6 + transform_shift;
-  E.q = kQuantScales[qp_scaled % 6];
-  double scale = 32768;
-  scale = transform_shift >= 0 ? scale / kPow2[2 * transform_shift] : scale * kPow2[-2 * transform_shift];
-  E.error_scale = scale / E.q / E.q;
-  const bool small = V->rq_cc != nullptr;        // the per-position cost arrays are in LDS (this wave's depth has them)
-  double *CC = small ? V->rq_cc : W->cost_coeff, *CS = small ? V->rq_cs : W->cost_sig, *C0 = W->cost_coeff0;
-#define RQ_LD(p) (small ? *(p) : CTU_GLOAD(p))
-  double *cost_cg_sig = (double *)V->t1;         // (the transform's other buffer: dead while a block is quantised; <= 64 groups)
-  const int cap_half = 1 << (E.q_bits - 1);
-  // ---- every position: candidate, level-0 cost; the last candidate in scan order ----
-#if defined(__HIPCC__) && defined(CTU_PROFILE)
-  unsigned long long tq = __builtin_amdgcn_s_memtime();
-#endif
-  int my_last = -1;
-  WFOR(sp, nn) {
-    const int blk = scan[sp];
-    const int64_t prod = (int64_t)iabs_((int)coef[blk]) * E.q;
-    const int32_t cap = 0x7fffffff - cap_half;
-    const int32_t level_double = (int32_t)(prod < cap ? prod : cap);
-    const int mal = (int)((uint32_t)(level_double + cap_half) >> E.q_bits);
-    const double err = (double)level_double;
-    C0[sp] = err * err * E.error_scale;
-    dst[blk] = (int16_t)mal;
-    if (mal > 0 && sp > my_last) my_last = sp;
-    if (sp < 64) V->cg_flag[sp] = 0;
-  }
-#if defined(__HIPCC__)
-  for (int o = 32; o >= 1; o >>= 1) { const int v = __shfl_xor(my_last, o, 64); my_last = v > my_last ? v : my_last; }
-#endif
-  const int last_scanpos = my_last;
-  WSYNC();
-  if (last_scanpos < 0) { if (CTU_TID == 0) V->rq_i[1] = 0; WSYNC(); return; }
-  RQ_T(12);
-  const int cg_last = last_scanpos >> 4;
-  // lane 0's running sums (rdo.c:1556-1583: the positions behind the last candidate only add their level-0 cost)
-  double block_uncoded_cost = 0, base_cost = 0;
-  if (CTU_TID == 0) {
-    for (int sp = nn - 1; sp > last_scanpos; --sp) { const double c = RQ_LD(&C0[sp]); block_uncoded_cost += c; base_cost += c; }
-    for (int g = 0; g <= cg_last; ++g) cost_cg_sig[g] = 0;
-    V->rq_i[4] = (int)((uint32_t)(nn * 28) >> 4);      // reg_bins
-    V->rq_i[5] = 1;                                    // regular bins remain
-  }
-  WSYNC();
-  RQ_T(13);
-  for (int cgs = cg_last; cgs >= 0; --cgs) {
-    const int first = scan[cgs * 16];
-    const int cg_pos_x = (first & (n - 1)) >> 2, cg_pos_y = (first >> l2) >> 2;
-    const int cg_blkpos = cg_pos_y * cgw + cg_pos_x;
-    int reg_bins = V->rq_i[4];
-    const int regular = V->rq_i[5];
-    // can the regular-bin budget run out inside this group?  (a position spends at most min(candidate, 2 -> 3) + 1 bins)
-    int fast = !regular;
-    if (regular) {
-      int bound = 0;
-      WFOR(sp, 16) {
-        const int scanpos = cgs * 16 + sp;
-        if (scanpos <= last_scanpos) { const int mal = dst[scan[scanpos]]; bound += (mal < 2 ? mal : 3) + (scanpos != last_scanpos); }
-      }
-#if defined(__HIPCC__)
-      for (int o = 8; o >= 1; o >>= 1) bound += __shfl_xor(bound, o, 64);
-      bound = __shfl(bound, 0, 64);
-#endif
-      fast = reg_bins - bound >= 4;
-    }
-    if (fast) {
-      // a position can be decided once the positions of its context template that may keep a level are decided; the others hold
-      // their final 0 already.  Lanes 0..15 own the group's scan positions; the rounds follow the chains of candidates (<= 7).
-#if defined(__HIPCC__)
-      {
-        const int sp = CTU_TID & 15, scanpos = cgs * 16 + sp;
-        const bool mine = CTU_TID < 16 && scanpos <= last_scanpos;
-        const int blk = scan[mine ? scanpos : cgs * 16];
-        const int mal0 = mine ? (int)dst[blk] : 0;
-        const unsigned nz = (unsigned)__ballot(mine && mal0 > 0) & 0xffffu;
-        const unsigned deps = (unsigned)S->deps4[sp] & nz;
-        int go_rice = 0;
-        if (mine && regular && sp != 15 && scanpos != last_scanpos) {
-          const int nb = scan[scanpos + 1];
-          go_rice = go_rice_par(template_abs_sum(coef, 4, nb & (n - 1), nb >> l2, n));      // sic: the INPUT coefficients (rdo.c:1697)
-        }
-        const double c0 = mine ? RQ_LD(&C0[scanpos]) : 0.0;
-        bool done = !mine;
-        unsigned decided = 0;
-        for (;;) {
-          const bool ready = !done && (deps & ~decided) == 0;
-          if (ready) {
-            int mal;
-            const rdoq_pos r = rdoq_decide(E, coef, dst, n, l2, color, blk, scanpos == last_scanpos, regular != 0, go_rice, c0, &mal);
-            dst[blk] = (int16_t)r.level;
-            V->rq_stage[sp] = r.cc; V->rq_stage[16 + sp] = r.cs;
-            done = true;
-          }
-          WSYNC();
-          decided = (unsigned)__ballot(done) & 0xffffu;
-          if (decided == 0xffffu) break;
-        }
-      }
-#else
-      {
-        unsigned nz = 0, decided = 0, all = 0;
-        for (int sp = 0; sp < 16; ++sp) { const int scanpos = cgs * 16 + sp; if (scanpos <= last_scanpos) { all |= 1u << sp; if (dst[scan[scanpos]] > 0) nz |= 1u << sp; } }
-        decided = ~all & 0xffffu;
-        while (decided != 0xffffu) {
-          const unsigned before = decided;
-          int16_t newlev[16];
-          for (int sp = 0; sp < 16; ++sp) {
-            if ((before >> sp) & 1) continue;
-            if (((unsigned)S->deps4[sp] & nz) & ~before) continue;
-            const int scanpos = cgs * 16 + sp, blk = scan[scanpos];
-            int go_rice = 0;
-            if (regular && sp != 15 && scanpos != last_scanpos) {
-              const int nb = scan[scanpos + 1];
-              go_rice = go_rice_par(template_abs_sum(coef, 4, nb & (n - 1), nb >> l2, n));
-            }
-            int mal;
-            const rdoq_pos r = rdoq_decide(E, coef, dst, n, l2, color, blk, scanpos == last_scanpos, regular != 0, go_rice, RQ_LD(&C0[scanpos]), &mal);
-            newlev[sp] = (int16_t)r.level;
-            V->rq_stage[sp] = r.cc; V->rq_stage[16 + sp] = r.cs;
-            decided |= 1u << sp;
-          }
-          for (int sp = 0; sp < 16; ++sp) if (((decided & ~before) >> sp) & 1) dst[scan[cgs * 16 + sp]] = newlev[sp];    // a round's levels appear together
-        }
-      }
-#endif
-    } else if (CTU_TID == 0) {
-      // the budget may run out in this group: position by position, exactly as the reference walks
-      int go_rice = 0;
-      for (int sp = 15; sp >= 0; --sp) {
-        const int scanpos = cgs * 16 + sp;
-        if (scanpos > last_scanpos) continue;
-        const int blk = scan[scanpos];
-        int mal;
-        const rdoq_pos r = rdoq_decide(E, coef, dst, n, l2, color, blk, scanpos == last_scanpos, reg_bins >= 4, go_rice, RQ_LD(&C0[scanpos]), &mal);
-        dst[blk] = (int16_t)r.level;
-        V->rq_stage[sp] = r.cc; V->rq_stage[16 + sp] = r.cs;
-        if ((scanpos % 16 == 0) && scanpos > 0) go_rice = 0;
-        else if (reg_bins >= 4) {
-          reg_bins -= (r.level < 2 ? r.level : 3) + (scanpos != last_scanpos);
-          go_rice = go_rice_par(template_abs_sum(coef, 4, blk & (n - 1), blk >> l2, n));
-        }
-      }
-      V->rq_i[4] = reg_bins;
-      V->rq_i[5] = reg_bins >= 4;
-    }
-    WSYNC();
-    RQ_T(14);
-    if (CTU_TID == 0) {
-      // the sums in scan order and the group's decision (rdo.c:1689-1772)
-      double rd_coded = 0, rd_uncoded = 0, rd_sig = 0, rd_sig0 = 0;
-      int nnz_before_pos0 = 0, flag = 0, spent = 0;
-      for (int sp = 15; sp >= 0; --sp) {
-        const int scanpos = cgs * 16 + sp;
-        if (scanpos > last_scanpos) continue;
-        const double cc = V->rq_stage[sp], cs = V->rq_stage[16 + sp], c0 = RQ_LD(&C0[scanpos]);
-        const int level = dst[scan[scanpos]];
-        block_uncoded_cost += c0;
-        base_cost += cc;
-        // (the first position of a group other than group 0 resets the Rice parameter INSTEAD of paying: rdo.c:1690-1697)
-        if (!(sp == 0 && cgs > 0)) spent += (level < 2 ? level : 3) + (scanpos != last_scanpos);
-        rd_sig += cs;
-        if (sp == 0) rd_sig0 = cs;
-        if (level) {
-          flag = 1;
-          rd_coded += cc - cs;
-          rd_uncoded += c0;
-          if (sp != 0) nnz_before_pos0++;
-        }
-      }
-      if (fast && regular) V->rq_i[4] = reg_bins - spent;
-      int zeroed = 0;
-      if (cgs) {
-        unsigned right = 0, lower = 0;
-        if (cg_pos_x + 1 < cgw) right = V->cg_flag[cg_blkpos + 1];
-        if (cg_pos_y + 1 < cgw) lower = V->cg_flag[cg_blkpos + cgw];
-        const int o_grp = M_SIGGRP + (E.t ? 2 : 0) + ((right || lower) ? 1 : 0);
-        if (!flag) {
-          cost_cg_sig[cgs] = lambda * rbits(E, o_grp, 0);
-          base_cost += cost_cg_sig[cgs] - rd_sig;
-        } else if (cgs < cg_last) {
-          if (nnz_before_pos0 == 0) { base_cost -= rd_sig0; rd_sig -= rd_sig0; }
-          double cost_zero_cg = base_cost;
-          cost_cg_sig[cgs] = lambda * rbits(E, o_grp, 1);
-          base_cost += cost_cg_sig[cgs];
-          cost_zero_cg += lambda * rbits(E, o_grp, 0);
-          cost_zero_cg += rd_uncoded;
-          cost_zero_cg -= rd_coded;
-          cost_zero_cg -= rd_sig;
-          if (cost_zero_cg < base_cost) {
-            flag = 0;
-            zeroed = 1;
-            base_cost = cost_zero_cg;
-            cost_cg_sig[cgs] = lambda * rbits(E, o_grp, 0);
-          }
-        }
-      } else {
-        flag = 1;
-      }
-      V->cg_flag[cg_blkpos] = (uint8_t)flag;
-      V->rq_i[6] = zeroed;
-    }
-    WSYNC();
-    RQ_T(15);
-    {
-      // the group's costs go to the per-position arrays the last-position search reads; a zeroed group's positions fall back to level 0
-      const int zeroed = V->rq_i[6];
-      WFOR(sp, 16) {
-        const int scanpos = cgs * 16 + sp;
-        if (scanpos <= last_scanpos) {
-          const int blk = scan[scanpos];
-          if (zeroed && dst[blk]) { dst[blk] = 0; CC[scanpos] = RQ_LD(&C0[scanpos]); CS[scanpos] = 0; }
-          else { CC[scanpos] = V->rq_stage[sp]; CS[scanpos] = V->rq_stage[16 + sp]; }
-        }
-      }
-    }
-    WSYNC();
-  }
-  RQ_T(16);
-  // ---- coded block flag and the last significant position (rdo.c:1774-1833) ----
-  if (CTU_TID == 0) {
-    double best_cost;
-    int best_last_idx_p1 = 0;
-    {
-      const int o_cbf = color == 0 ? (CTU_RQ_ROOT(V) ? 243 : M_CBF_LUMA) : color == 1 ? M_CBF_CB : M_CBF_CR + (cbf_u ? 1 : 0);
-      best_cost = block_uncoded_cost + lambda * rbits(E, o_cbf, 0);
-      base_cost += lambda * rbits(E, o_cbf, 1);
-    }
-    const int32_t *last_x_bits = S->last_bits + last_bits_off(E.t, l2, 0), *last_y_bits = S->last_bits + last_bits_off(E.t, l2, 1);
-    int found_last = 0;
-    for (int cgs = cg_last; cgs >= 0; cgs--) {
-      const int first = scan[cgs * 16];
-      const int cg_blkpos = ((first >> l2) >> 2) * cgw + ((first & (n - 1)) >> 2);
-      base_cost -= cost_cg_sig[cgs];
-      if (V->cg_flag[cg_blkpos]) {
-        for (int sp = 15; sp >= 0; sp--) {
-          const int scanpos = cgs * 16 + sp;
-          if (scanpos > last_scanpos) continue;
-          const int blkpos = scan[scanpos];
-          if (dst[blkpos]) {
-            const int pos_y = blkpos >> l2, pos_x = blkpos - (pos_y << l2);
-            const int cx = group_idx(pos_x), cy = group_idx(pos_y);
-            double cl = last_x_bits[cx] + last_y_bits[cy];
-            if (cx > 3) cl += 32768 * ((cx - 2) >> 1);
-            if (cy > 3) cl += 32768 * ((cy - 2) >> 1);
-            const double cost_last = lambda * cl;
-            const double total = base_cost + cost_last - RQ_LD(&CS[scanpos]);
-            if (total < best_cost) { best_last_idx_p1 = scanpos + 1; best_cost = total; }
-            if (dst[blkpos] > 1) { found_last = 1; break; }
-            base_cost -= RQ_LD(&CC[scanpos]);
-            base_cost += RQ_LD(&C0[scanpos]);
-          } else {
-            base_cost -= RQ_LD(&CS[scanpos]);
-          }
-        }
-        if (found_last) break;
-      }
-    }
-    V->rq_i[0] = best_last_idx_p1;
-    V->rq_i[1] = best_last_idx_p1 > 0;
-  }
-  WSYNC();
-  RQ_T(17);
-  const int best_last_idx_p1 = V->rq_i[0];
-  WFOR(scanpos, last_scanpos + 1) {
-    const int b = scan[scanpos];
-    if (scanpos < best_last_idx_p1) { const int level = dst[b]; dst[b] = (int16_t)((coef[b] < 0) ? -level : level); }
-    else dst[b] = 0;
-  }
-  WSYNC();
-  RQ_T(18);
-}
+#include "ctu_rdoq_emul.h"
 #else
 // uvg_rdoq (rdo.c:1449-1870) by one wave: same arithmetic as rdoq_serial, restructured around what is sequential in it.
 //   * every position's quantisation candidate: all positions at once;
@@ -1651,12 +1382,10 @@ template <typename PX> CTU_INLINE1 CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W
   double *cost_cg_sig = (double *)V->t1;         // (the transform's other buffer: dead while a block is quantised; <= 64 groups)
   const int cap_half = 1 << (E.q_bits - 1);
   const int32_t cap = 0x7fffffff - cap_half;
-#if defined(CTU_PROFILE)
-  unsigned long long tq = __builtin_amdgcn_s_memtime();
-#endif
+  RQ_T0(W)
   // ---- every position: candidate; the last candidate in scan order ----
   int my_last = -1;
-  WFOR(sp, nn) {
+  PAR_FOR(sp, nn) {
     const int blk = scan[sp];
     const int64_t prod = (int64_t)iabs_((int)coef[blk]) * E.q;
     const int32_t level_double = (int32_t)(prod < cap ? prod : cap);
@@ -1667,8 +1396,8 @@ template <typename PX> CTU_INLINE1 CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W
   }
   for (int o = 32; o >= 1; o >>= 1) { const int v = __shfl_xor(my_last, o, 64); my_last = v > my_last ? v : my_last; }
   const int last_scanpos = my_last;
-  WSYNC();
-  if (last_scanpos < 0) { if (CTU_TID == 0) V->rq_i[1] = 0; WSYNC(); return; }
+  CTU_SYNC();
+  if (last_scanpos < 0) { if (CTU_TID == 0) V->rq_i[1] = 0; CTU_SYNC(); return; }
   RQ_T(12);
   const int cg_last = last_scanpos >> 4;
   const int lane = CTU_TID, sp = lane & 15;
@@ -1685,7 +1414,7 @@ template <typename PX> CTU_INLINE1 CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W
   }
   if (CTU_TID == 0) for (int g = 0; g <= cg_last; ++g) cost_cg_sig[g] = 0;
   int reg_bins = (int)((uint32_t)(nn * 28) >> 4);
-  WSYNC();
+  CTU_SYNC();
   RQ_T(13);
   double f_cc = 0, f_cs = 0, f_c0 = 0;          // cg_last == 0 (every 4x4 block, sparse larger ones): the group's numbers stay in
   int f_lev = 0;                                 // registers for the last-position search -- no cost arrays
@@ -1728,10 +1457,10 @@ template <typename PX> CTU_INLINE1 CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W
           changed = r.level != lev;
           lev = r.level;
         }
-        WSYNC();                               // every lane has read the levels it needs
+        CTU_SYNC();                               // every lane has read the levels it needs
         if (changed) dst[blk] = (int16_t)lev;
         const bool any = __ballot(changed) != 0;
-        WSYNC();
+        CTU_SYNC();
         if (!any) break;
       }
     } else {
@@ -1756,10 +1485,10 @@ template <typename PX> CTU_INLINE1 CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W
         }
         V->rq_i[4] = rb;
       }
-      WSYNC();
+      CTU_SYNC();
       if (mine) { cc = V->rq_stage[sp]; cs = V->rq_stage[16 + sp]; lev = dst[blk]; }
       reg_bins = V->rq_i[4];
-      WSYNC();
+      CTU_SYNC();
     }
     RQ_T(14);
     // the sums in scan order and the group's decision (rdo.c:1689-1772): every lane, from the owners' registers
@@ -1812,7 +1541,7 @@ template <typename PX> CTU_INLINE1 CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W
           cgc = lambda * rbits(E, o_grp, 0);
         }
       }
-      WSYNC();                                 // (the neighbours' flags are read)
+      CTU_SYNC();                                 // (the neighbours' flags are read)
       if (CTU_TID == 0) cost_cg_sig[cgs] = cgc;
     } else {
       flag = 1;
@@ -1825,7 +1554,7 @@ template <typename PX> CTU_INLINE1 CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W
       if (zeroed && lev) dst[blk] = 0;
       if (small) { CCl[scanpos] = wc; CSl[scanpos] = ws; } else { CCg[scanpos] = wc; CSg[scanpos] = ws; }
     }
-    WSYNC();
+    CTU_SYNC();
     RQ_T(15);
   }
   RQ_T(16);
@@ -1886,12 +1615,12 @@ template <typename PX> CTU_INLINE1 CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W
   }
   if (CTU_TID == 0) V->rq_i[1] = best_last_idx_p1 > 0;
   RQ_T(17);
-  WFOR(scanpos, last_scanpos + 1) {
+  PAR_FOR(scanpos, last_scanpos + 1) {
     const int b = scan[scanpos];
     if (scanpos < best_last_idx_p1) { const int level = dst[b]; dst[b] = (int16_t)((coef[b] < 0) ? -level : level); }
     else dst[b] = 0;
   }
-  WSYNC();
+  CTU_SYNC();
   RQ_T(18);
 }
 #endif
@@ -2090,7 +1819,7 @@ template <typename PX, bool OOL = false> CTU_INLINE1 CTU_DEV int recon_tu_inl(ld
   CTU_GLB const PX *Sp = src_block(J, color, lx >> c, ly >> c, &sps);
   const int depth = (int)px_info<PX>::depth;
 #if defined(CTU_PB)
-  LANE0 V->rq_root = (flags & 4) && color == 0;
+  SERIAL V->rq_root = (flags & 4) && color == 0;
   if (!(flags & 1))
 #endif
   { CTU_T0();
@@ -2107,7 +1836,7 @@ template <typename PX, bool OOL = false> CTU_INLINE1 CTU_DEV int recon_tu_inl(ld
 #if defined(__HIPCC__)
     nz = __ballot(nz) != 0;
 #endif
-    LANE0 V->rq_i[1] = nz;
+    SERIAL V->rq_i[1] = nz;
     CTU_SYNC();
   } else
 #endif
@@ -2181,7 +1910,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void ssd_block(lds<PX> *S, const job
   PAR_FOR(e, w * w) { const int r = e >> l2, q = e & (w - 1); const int d = (int)Sp[r * sps + q] - (int)rec[r * rp + q]; acc += d * d; }
 #if defined(__HIPCC__)
   for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  LANE0 V->red[slot] = acc >> (2 * ((int)px_info<PX>::depth - 8));
+  SERIAL V->red[slot] = acc >> (2 * ((int)px_info<PX>::depth - 8));
 #else
   V->red[slot] = acc >> (2 * ((int)px_info<PX>::depth - 8));
 #endif
@@ -2261,115 +1990,8 @@ template <typename PX> CTU_NOINLINE CTU_DEV void mark_deblocking(lds<PX> *S, int
 // regular bins a scan position spends, from its record (level in bits 0..15, "its sig flag is coded" in bit 29)
 CTU_DEV int rec_spend(uint32_t rec) { const uint32_t a = rec & 0xffffu; return (int)((rec >> 29) & 1u) + (a ? 1 + (a > 1 ? 2 : 0) : 0); }
 
-#if defined(CTU_LEAF4)
-#include "ctu_leaf4.h"
-#endif
-
 #if defined(__HIPCC__)
-// coeff_bits for a 4x4 block (one coefficient group): the shape the 4x4 leaves, their 8x8 areas' chroma and most of the coder
-// pass consist of.  Same bins and adaptation as the general function below, but nothing goes through memory: lane sp (0..15) holds
-// position sp's record, the budget of regular bins is a lane sum, the models' sweep (one: 12 + 3 * 16 luma / 8 + 3 * 11 chroma
-// models) hands the records out with v_readlane and runs branch-free.
-template <typename PX> CTU_DEV double coeff_bits4(lds<PX> *S, CTU_LDS uint32_t *m, int update, CTU_LDS const int16_t *coeff, int color)
-{
-  const int lane = CTU_TID, sp = lane & 15, t = color ? 1 : 0;
-  const uint16_t *scan = scan_of(S, 2);
-  const int blk = scan[sp], py = blk >> 2, px = blk & 3;
-  const int a = iabs_((int)coeff[blk]);
-  const unsigned nzmask = (unsigned)__ballot(a != 0) & 0xffffu;
-  if (nzmask == 0) return 0.0;
-  const int last = 31 - __clz((int)nzmask);
-  int diag, tsum;
-  int ctx_sig = sig_ctx_abs(coeff, px, py, 4, color, &diag, &tsum);
-  if (t && ctx_sig > 7) ctx_sig = 7;
-  int ofs = 0;
-  if (sp != last) ofs = ((tsum < 4 ? tsum : 4) + 1) + (!diag ? (color == 0 ? 15 : 5) : color == 0 ? (diag < 3 ? 10 : (diag < 10 ? 5 : 0)) : 0);
-  const int r4 = go_rice_par((unsigned)abs_sum_tmpl(coeff, px, py, 4, 4)), r0 = go_rice_par((unsigned)abs_sum_tmpl(coeff, px, py, 4, 0));
-  const bool live = sp <= last;
-  const int sig_coded = live && sp != last;
-  const int spend = live ? sig_coded + (a ? 1 + (a > 1 ? 2 : 0) : 0) : 0;
-  const uint32_t rec = (uint32_t)(a > 0xffff ? 0xffff : a) | (uint32_t)ctx_sig << 16 | (uint32_t)ofs << 20 | (uint32_t)sig_coded << 29;
-  // where the regular-bin budget (28 for 16 coefficients) runs out: positions <= sw are bypass-coded
-  int tot = spend;
-  for (int o = 8; o >= 1; o >>= 1) tot += __shfl_xor(tot, o, 64);
-  int sw = -1;
-  if (28 - tot < 4) {
-    int rb = 28;
-    for (int j = last; j >= 0; --j) {
-      if (rb < 4) { sw = j; break; }
-      rb -= __builtin_amdgcn_readlane(spend, j);
-    }
-  }
-  // ---- the models, one per lane ----
-  const int nk0 = t ? 8 : 12, nks = t ? 11 : 16;
-  int role = -1, k = 0;
-  if (lane < nk0) { role = 0; k = lane; }
-  else if (lane < nk0 + 3 * nks) { role = 1 + (lane - nk0) / nks; k = (lane - nk0) % nks; }
-  if (!t && role > 0 && k > 0) k += 5;          // 4x4 luma: set offsets 0, 6..20
-  const int model = role < 0 ? 0 : (role == 0 ? M_SIG + 12 * t : role == 1 ? M_GT1 + 21 * t : role == 2 ? M_PAR + 21 * t : M_GT2 + 21 * t) + k;
-  uint32_t st = m[model];
-  const int rw = kRate[model], r0w = rw >> 4, r1w = rw & 15;
-  const uint32_t add0 = (0x7fffu >> r0w) & 0x7fe0u, add1 = (0x7fffu >> r1w) & 0x7ffeu;
-  const uint32_t fsh = role == 0 ? 16 : 20, fmask = role == 0 ? 15u : 31u, rsel = role < 0 ? 31u : (uint32_t)role;
-  CTU_LDS const uint32_t *const ebits = LDSP(const uint32_t, tab_ebits());
-  uint32_t acc = 0;
-  for (int j = last; j > sw; --j) {
-    const uint32_t rj = (uint32_t)__builtin_amdgcn_readlane((int)rec, j);
-    const uint32_t aj = rj & 0xffffu;
-    // per role: does the position code a bin with one of the role's models, and which   (sig, gt1, parity, gt2)
-    const uint32_t gates = ((rj >> 29) & 1u) | (aj != 0 ? 2u : 0u) | (aj > 1 ? 12u : 0u);
-    if (gates == 0) continue;
-    const uint32_t bins = (aj != 0 ? 1u : 0u) | (aj > 1 ? 2u : 0u) | ((aj & 1u) << 2) | (aj >= 4 ? 8u : 0u);
-    const bool hit = ((gates >> rsel) & 1u) && ((rj >> fsh) & fmask) == (uint32_t)k;
-    const uint32_t bin = (bins >> rsel) & 1u;
-    uint32_t s0 = st & 0xffffu, s1 = st >> 16;
-    const uint32_t cost = ebits[(((s0 + s1) >> 8) << 1) ^ bin];
-    s0 -= (s0 >> r0w) & 0x7fe0u;
-    s1 -= (s1 >> r1w) & 0x7ffeu;
-    s0 += bin ? add0 : 0u;
-    s1 += bin ? add1 : 0u;
-    st = hit ? ((s0 & 0xffffu) | (s1 << 16)) : st;
-    acc += hit ? cost : 0u;
-  }
-  if (role >= 0 && update) m[model] = st;
-  unsigned long long q15 = acc;
-  // ---- bypass-coded parts: remainders, bypass positions, signs ----
-  int ibits = 0;
-  if (lane < 16 && live) {
-    if (sp > sw) { if (a >= 4) ibits += coeff_remain_bits(((unsigned)a - 4) >> 1, (uint32_t)r4, 5); }
-    else {
-      const unsigned pos0 = 1u << r0;
-      ibits += coeff_remain_bits(a == 0 ? pos0 : ((unsigned)a <= pos0 ? (unsigned)a - 1 : (unsigned)a), (uint32_t)r0, 5);
-    }
-    ibits += a != 0;
-  }
-  // ---- lane 0: the last-position prefix (its models are nobody else's; counting only: on a copy) ----
-  if (lane == 0) {
-    double bits = 0;
-    CTU_LDS uint32_t *mk = m;
-    if (!update) {
-#if defined(CTU_PB)
-      mk = LDSP(uint32_t, CTU_WAVE == 0 ? S->pb.cnt_models : (CTU_WAVE == 1 ? S->pb.work0 : pbq(S).cnt_models));      // (the leaf wave counts on the 64x64 candidate's set: idle once the walk is below depth 0)
-#else
-      mk = LDSP(uint32_t, S->work[2]);
-#endif
-      for (int i = M_LASTX; i < M_CBF_LUMA; ++i) mk[i] = m[i];
-    }
-    const int pos_last = scan[last], last_y = pos_last >> 2, last_x = pos_last & 3;
-    const int bx = M_LASTX + 20 * t, by = M_LASTY + 20 * t;      // 4x4: prefix offset 0, shift 0, three prefix models per axis
-    for (int q = 0; q < last_x; q++) m_code(mk, 1, bx + q, 1, bits);
-    if (last_x < 3) m_code(mk, 1, bx + last_x, 0, bits);
-    for (int q = 0; q < last_y; q++) m_code(mk, 1, by + q, 1, bits);
-    if (last_y < 3) m_code(mk, 1, by + last_y, 0, bits);
-    q15 += (unsigned long long)(bits * 32768.0);
-  }
-  for (int o = 32; o >= 1; o >>= 1) {
-    q15 += __shfl_xor(q15, o, 64);
-    ibits += __shfl_xor(ibits, o, 64);
-  }
-  WSYNC();
-  return (double)q15 / 32768.0 + (double)ibits;
-}
+#include "ctu_leaf4.h"
 #endif
 
 // Coefficient bit cost by the first wave (same bins, same model adaptation as coeff_bits_serial).  What is sequential in the
@@ -2394,18 +2016,11 @@ template <typename PX> CTU_NOINLINE CTU_DEV double coeff_bits(lds<PX> *S, uint32
   const uint16_t *scan = scan_of(S, l2);
   CTU_LDS uint32_t *const m = (CTU_LDS uint32_t *)m_;
   typename mg_ptr<PX, const int16_t>::type const coeff = MGP(PX, const int16_t, coeff_);
-#if defined(CTU_LEAF4)
-  if (n == 4) return coeff_bits4r(S, m, update, (int)coeff[lane & 15], color);
-#else
-  if (n == 4) return coeff_bits4(S, m, update, coeff, color);
-#endif
+  if (n == 4) return coeff_bits4r(S, m, update, (int)coeff[lane & 15], color);          // (ctu_leaf4.h: the block from registers)
   CTU_LDS uint32_t *recs = (CTU_LDS uint32_t *)(V->t0);       // t0 + t1: 1024 words, free while costs are counted
   CTU_LDS uint8_t *cgf = (CTU_LDS uint8_t *)V->cg_flag;                                   // per group (raster): has a level
   CTU_LDS int32_t *gtot = (CTU_LDS int32_t *)(V->rq_stage);   // per group (scan order): regular bins it would spend, bit 30: a level among k = 1..15
-#if defined(CTU_PROFILE)
-  scratch *const W = S->prof_w;
-  unsigned long long tq = __builtin_amdgcn_s_memtime();
-#endif
+  RQ_T0(S->prof_w)
   // ---- last significant position, group flags ----
   int my_last = -1;
   for (int sp = lane; sp < nn; sp += 64) if (coeff[scan[sp]]) my_last = sp;
@@ -2420,7 +2035,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV double coeff_bits(lds<PX> *S, uint32
     cgf[((f >> l2) >> 2) * cgw + ((f & (n - 1)) >> 2)] = (uint8_t)(any0 | anyr);
     gtot[g] = anyr << 30;
   }
-  WSYNC();
+  CTU_SYNC();
   RQ_T(28);
   // ---- per position: level, contexts, Rice parameters, whether its sig flag is coded, the regular bins it would spend ----
   for (int sp = lane; sp <= last; sp += 64) {
@@ -2438,13 +2053,13 @@ template <typename PX> CTU_NOINLINE CTU_DEV double coeff_bits(lds<PX> *S, uint32
     recs[sp] = (uint32_t)(a > 0xffff ? 0xffff : a) | (uint32_t)ctx_sig << 16 | (uint32_t)ofs << 20 | (uint32_t)r4 << 25 | (uint32_t)r0 << 27 |
                (uint32_t)sig_coded << 29;
   }
-  WSYNC();
+  CTU_SYNC();
   for (int g = lane; g <= cg_last; g += 64) {
     int tot = 0;
     for (int k = 0; k < 16; ++k) if (g * 16 + k <= last) tot += rec_spend(recs[g * 16 + k]);
     gtot[g] = (gtot[g] & (1 << 30)) | tot;
   }
-  WSYNC();
+  CTU_SYNC();
   // ---- where the regular-bin budget runs out (lane 0; whole groups while they fit) ----
   if (lane == 0) {
     int rb = (nn * 28) >> 4, sw = -1;
@@ -2462,7 +2077,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV double coeff_bits(lds<PX> *S, uint32
     }
     V->rq_i[8] = sw;
   }
-  WSYNC();
+  CTU_SYNC();
   const int sw = V->rq_i[8];          // scan positions <= sw are bypass-coded
   RQ_T(29);
   // ---- the models, one per lane, along the positions in coding order ----
@@ -2566,16 +2181,14 @@ template <typename PX> CTU_NOINLINE CTU_DEV double coeff_bits(lds<PX> *S, uint32
 #if defined(CTU_PB)
       mk = (CTU_LDS uint32_t *)(CTU_WAVE == 0 ? S->pb.cnt_models : (CTU_WAVE == 1 ? S->pb.work0 : pbq(S).cnt_models));       // (every work[] set is some depth's here; the leaf wave: see coeff_bits)
       mg = mk;
+      for (int i = 0; i < 4; ++i) mk[M_SIGGRP + i] = m[M_SIGGRP + i];
+      for (int i = M_LASTX; i < M_CBF_LUMA; ++i) mk[i] = m[i];
 #else
       // (the 64x64 candidate, counted beside the walk by two waves at a time while every work[] set is some depth's: the 84 models live in
       // the wave's reference rows -- a block is counted after its reconstruction -- behind the 4 group-flag models)
       mk = (CTU_LDS uint32_t *)V->top - (M_LASTX - 4);
       mg = (CTU_LDS uint32_t *)V->top;
       for (int i = 0; i < 4; ++i) mg[M_SIGGRP + i] = m[M_SIGGRP + i];
-      for (int i = M_LASTX; i < M_CBF_LUMA; ++i) mk[i] = m[i];
-#endif
-#if defined(CTU_PB)
-      for (int i = 0; i < 4; ++i) mk[M_SIGGRP + i] = m[M_SIGGRP + i];
       for (int i = M_LASTX; i < M_CBF_LUMA; ++i) mk[i] = m[i];
 #endif
     }
@@ -2609,7 +2222,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV double coeff_bits(lds<PX> *S, uint32
     q15 += __shfl_xor(q15, o, 64);
     ibits += __shfl_xor(ibits, o, 64);
   }
-  WSYNC();
+  CTU_SYNC();
   RQ_T(31);
   return (double)q15 / 32768.0 + (double)ibits;
 #endif
@@ -2623,7 +2236,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV double tr_cost(lds<PX> *S, const par
   // called by all lanes of the first wave; the flag bins are lane 0's, the coefficient costs the wave's
   double coeff_bits_ = 0, luma_bits = 0, chroma_bits = 0;
   const int cb_y = cbf & 1, cb_u = (cbf >> 1) & 1, cb_v = (cbf >> 2) & 1;
-  LANE0 {
+  SERIAL {
     CTU_LDS uint32_t *const m = LDSP(uint32_t, V->cur);
     if (has_chroma) {
       m_code(m, update, M_CBF_CB + 0, cb_u, chroma_bits);
@@ -2631,7 +2244,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV double tr_cost(lds<PX> *S, const par
     }
     m_code(m, update, M_CBF_LUMA + 0, cb_y, luma_bits);
   }
-  WSYNC();
+  CTU_SYNC();
   const unsigned luma_ssd = (unsigned)V->red[0];
   // uvg_get_coeff_cost counts on a copy of the models that is kept only when update is set (rdo.c:322-356)
   if (cb_y) coeff_bits_ += coeff_bits(S, V->cur, update, lv_of(V, 0), n, 0);
@@ -2694,10 +2307,10 @@ template <typename PX> CTU_DEV void help_run(lds<PX> *S, const job<PX> &J)      
   const int lx = cx & 63, ly = cy & 63;
   PX *const ru = S->Du + ((ly >> 1) + 1) * PC + (lx >> 1) + 1;
   int16_t *const ku = J.coeff + 4096 + (ly >> 1) * LCU_C + (lx >> 1);
-#if defined(CTU_LEAF4)
+#if defined(__HIPCC__)
   const lf_block B = leaf_recon(S, J, wv_of(S), 1, mode, 0, cx, cy, lx, ly, 8, 0, ru, PC, ku, LCU_C);
   const int has = B.has;
-  LANE0 S->help[4] = B.ssd;
+  SERIAL S->help[4] = B.ssd;
 #else
   const int has = recon_tu(S, J, 1, cx, cy, lx, ly, 8, mode, 0, ru, PC, ku, LCU_C, 8);
 #endif
@@ -2706,7 +2319,7 @@ template <typename PX> CTU_DEV void help_run(lds<PX> *S, const job<PX> &J)      
     CTU_LDS int16_t *const to = LDSP(int16_t, S->wv[0].lv1);
     PAR_FOR(e, 16) to[e] = from[e];
   }
-  LANE0 S->help[3] = has;
+  SERIAL S->help[3] = has;
   CTU_SYNC();
 #if defined(__HIPCC__)
   __builtin_amdgcn_s_setprio(0);
@@ -2717,9 +2330,9 @@ template <typename PX> CTU_DEV bool help_post(lds<PX> *S, const job<PX> &J, int 
 {
 #if defined(__HIPCC__)
   if (__builtin_amdgcn_readfirstlane(mb_load(&S->done[3]) == S->req[3]) == 0) return false;
-  LANE0 { S->help[0] = cx; S->help[1] = cy; S->help[2] = mode; }
+  SERIAL { S->help[0] = cx; S->help[1] = cy; S->help[2] = mode; }
   CTU_SYNC();
-  LANE0 mb_store(&S->hreq, S->hreq + 1);
+  SERIAL mb_store(&S->hreq, S->hreq + 1);
   return true;
 #else
   if (g_emul_lazy) return false;                   // (the host tests take both roads)
@@ -2754,9 +2367,9 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu(lds<PX> *S, const job<P
   const int sep = n == 4;                                 // a 4x4 CU: its chroma belongs to the 8x8 area, carried by the fourth one
   const int has_chroma = N.has_chroma;
   if (to_cand) {
-    LANE0 V->cur = S->work[L - 1];             // (the walk put the CU's entry models there before posting the request)
+    SERIAL V->cur = S->work[L - 1];             // (the walk put the CU's entry models there before posting the request)
   } else {
-    LANE0 {
+    SERIAL {
       V->cur = S->cur;
       cu4 *c = cu_at(S, lx, ly);                           // the CU's own entry is reset (search.c:1371-1388)
       c->type = CU_NOTSET; c->cbf = 0; c->luma_edges = 0; c->chroma_edges = 0; c->mode = 0; c->mode_chroma = 0; c->log2 = (uint8_t)ilog2_dev(n);
@@ -2780,7 +2393,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu(lds<PX> *S, const job<P
   const int mode = V->u_mode;
 #endif
   if (!to_cand) { SERIAL fill_cu(S, lx, ly, n, mode, mode, sep ? 2 : ilog2_dev(n) - 1, N.split_tree, cu_mtt(N.mode_type_tree, L)); CTU_SYNC(); }
-#if defined(CTU_LEAF4X)
+#if defined(__HIPCC__) && !defined(CTU_PB)
   if (n == 8 && !to_cand) leaf_load_area(S, J, lx, ly);          // (an 8x8 leaf: the walk's own wave)
 #endif
   // where the three blocks are reconstructed and where their levels go
@@ -2805,9 +2418,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu(lds<PX> *S, const job<P
   int cbf = 0;
 #if !defined(CTU_PB)
   const bool helped = sep && has_chroma && !to_cand && help_post(S, J, cx, cy, mode);
-#if defined(__HIPCC__) && defined(CTU_PROFILE)
-  if (sep && has_chroma && !to_cand) { LANE0 J.W->prof[1][helped ? 19 : 20] += 1; }
-#endif
+  CTU_HELPED(J.W, sep && has_chroma && !to_cand, helped)
 #else
   const bool helped = false;
 #endif
@@ -2818,22 +2429,18 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu(lds<PX> *S, const job<P
     const bool c = color != 0;
 #if !defined(CTU_PB)
     if (helped && color == 1) {
-#if defined(__HIPCC__) && defined(CTU_PROFILE)
-      const unsigned long long tw = __builtin_amdgcn_s_memtime();
-#endif
+      CTU_TW0()
       cbf |= help_wait(S) << 1;
-#if defined(__HIPCC__) && defined(CTU_PROFILE)
-      LANE0 J.W->prof[1][21] += __builtin_amdgcn_s_memtime() - tw;
-#endif
+      CTU_TW1(J.W)
       continue;
     }
 #endif
-#if defined(CTU_LEAF4X)
+#if defined(__HIPCC__) && !defined(CTU_PB)
     if (c && n == 8) {
       // the 4x4 chroma blocks of an 8x8 CU: the register-resident block of ctu_leaf4.h (the area's source samples are in S->lf_src)
       CTU_T0();
       const lf_block B = leaf_recon(S, J, V, color, mode, color == 2 ? (cbf >> 1) & 1 : 0, x, y, lx, ly, 8, 0, color == 1 ? ru : rv, rpc, color == 1 ? ku : kv, kpc);
-      LANE0 V->red[color] = B.ssd;
+      SERIAL V->red[color] = B.ssd;
       cbf |= B.has << color;
       CTU_T1(J.W, 3);
       continue;
@@ -2843,8 +2450,8 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu(lds<PX> *S, const job<P
                                  color == 0 ? ry : (color == 1 ? ru : rv), c ? rpc : rpy, color == 0 ? ky : (color == 1 ? ku : kv), c ? kpc : kpy, c ? area : n);
     cbf |= has << color;
   }
-#if defined(CTU_LEAF4X)
-  if (has_chroma && n != 8)
+#if defined(__HIPCC__) && !defined(CTU_PB)
+  if (has_chroma && n != 8)          // (an 8x8 CU's chroma blocks: their SSDs came with the blocks, above)
 #else
   if (has_chroma)
 #endif
@@ -2860,7 +2467,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu(lds<PX> *S, const job<P
   CTU_T0();
   {
     double bits = 0;
-    LANE0 {
+    SERIAL {
       if (!to_cand) {
         cu4 *c = cu_at(S, lx, ly);
         c->cbf = (uint8_t)(cbf & 1);
@@ -2888,7 +2495,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu(lds<PX> *S, const job<P
     }
     CTU_SYNC();
     const double trc = tr_cost(S, P, 1, n, cbf, has_chroma, cn);       // cu_rd_cost_tr_split_accurate (:1718)
-    LANE0 {
+    SERIAL {
       double cost = bits * P.lambda;
       cost += trc;
       if (!to_cand) mark_deblocking(S, x, y, lx, ly, n, sep, has_chroma);
@@ -2899,7 +2506,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu(lds<PX> *S, const job<P
   CTU_T1(J.W, 5);
 }
 
-#if defined(CTU_LEAF4)
+#if defined(__HIPCC__)
 // eval_cu(S, J, 4, 0) for the 4x4 CU described by lvl[4] on the register-resident formulation of ctu_leaf4.h: same decisions, same
 // models, same reconstruction; the walk's wave, on wv[0].
 template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu4(lds<PX> *S, const job<PX> &J)
@@ -2909,7 +2516,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu4(lds<PX> *S, const job<
   level_state &N = S->lvl[4];
   const int x = N.x, y = N.y, lx = x & 63, ly = y & 63;
   const int has_chroma = N.has_chroma;
-  LANE0 {
+  SERIAL {
     V->cur = S->cur;
     cu4 *c = cu_at(S, lx, ly);                           // the CU's own entry is reset (search.c:1371-1388)
     c->type = CU_NOTSET; c->cbf = 0; c->luma_edges = 0; c->chroma_edges = 0; c->mode = 0; c->mode_chroma = 0; c->log2 = 2; c->log2_c = 2;
@@ -2927,7 +2534,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu4(lds<PX> *S, const job<
   LF_T(1);
   mode = leaf_rough(S, J, V, x, y, lx, ly, leaf_src(S, 0, lx, ly), mpm);
   CTU_T1(J.W, 0); }
-  LANE0 {          // lcu_fill_cu_info (search.c:314-353) for the one entry of a 4x4 CU
+  SERIAL {          // lcu_fill_cu_info (search.c:314-353) for the one entry of a 4x4 CU
     cu4 *c = cu_at(S, lx, ly);
     c->type = CU_INTRA; c->log2 = 2; c->log2_c = 2; c->mode = (int8_t)mode; c->mode_chroma = (int8_t)mode;
 #if defined(CTU_PB)
@@ -2947,9 +2554,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu4(lds<PX> *S, const job<
   const bool helped = false;              // (no chroma helper: the P / B CTU has no depth waves)
 #else
   const bool helped = has_chroma && help_post(S, J, cx, cy, mode);
-#if defined(CTU_PROFILE)
-  if (has_chroma) { LANE0 J.W->prof[1][helped ? 19 : 20] += 1; }
-#endif
+  CTU_HELPED(J.W, has_chroma, helped)
 #endif
   int ssd_y = 0, ssd_u = 0, ssd_v = 0, cbf = 0, lev_y = 0, lev_u = 0, lev_v = 0;
   { CTU_T0();
@@ -2957,15 +2562,11 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu4(lds<PX> *S, const job<
   for (int color = 0; color < (has_chroma ? 3 : 1); ++color) {          // ONE call site of the block function (see leaf_recon)
 #if !defined(CTU_PB)
     if (helped && color == 1) {
-#if defined(CTU_PROFILE)
-      const unsigned long long tw = __builtin_amdgcn_s_memtime();
-#endif
+      CTU_TW0()
       cbf |= help_wait(S) << 1;
       ssd_u = S->help[4];
       lev_u = (int)LDSP(const int16_t, V->lv1)[CTU_TID & 15];         // (help_run left the levels in the walk's scratch)
-#if defined(CTU_PROFILE)
-      LANE0 J.W->prof[1][21] += __builtin_amdgcn_s_memtime() - tw;
-#endif
+      CTU_TW1(J.W)
       continue;
     }
 #endif
@@ -2980,7 +2581,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu4(lds<PX> *S, const job<
   LF_T(9);
   // ---- the CU's side information and RD cost (search.c:1700-1774) ----
   double bits = 0;
-  LANE0 {
+  SERIAL {
     cu4 *c = cu_at(S, lx, ly);
     c->cbf = (uint8_t)(cbf & 1);
     // mark_deblocking (search.c:1075-1174) for a 4x4 CU: its own luma edges; the area's chroma edges with the CU that carries the chroma
@@ -3028,7 +2629,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu4(lds<PX> *S, const job<
     if (has_chroma) { tbits += coeff_bits4r(S, m, 1, lev_u, 1); tbits += coeff_bits4r(S, m, 1, lev_v, 2); }
   }
   LF_T(12);
-  LANE0 {
+  SERIAL {
     const unsigned chroma_ssd = has_chroma ? (unsigned)((unsigned)ssd_u * P.chroma_weight_u) + (unsigned)((unsigned)ssd_v * P.chroma_weight_v) : 0u;
     const double trc = (unsigned)ssd_y * 1.0 + chroma_ssd * 1.0 + tbits * P.lambda;
     double cost = bits * P.lambda;
@@ -3211,7 +2812,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV int recon_tu64(lds<PX> *S, const job
 #if defined(__HIPCC__)
   for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
 #endif
-  LANE0 V->red[color] = acc >> (2 * (depth - 8));
+  SERIAL V->red[color] = acc >> (2 * (depth - 8));
   CTU_SYNC();
   return has;
 }
@@ -3222,10 +2823,10 @@ template <typename PX> CTU_NOINLINE CTU_DEV void luma64_step(lds<PX> *S, const j
   wctx *const V = wv_of(S);
   const int cy = recon_tu64(S, J, 0, i, S->m64[0], 0, V->lv0);
   double by = 0;
-  LANE0 m_code(LDSP(uint32_t, S->coder), 0, M_CBF_LUMA + 0, cy, by);
-  WSYNC();
+  SERIAL m_code(LDSP(uint32_t, S->coder), 0, M_CBF_LUMA + 0, cy, by);
+  CTU_SYNC();
   if (cy) by += coeff_bits(S, S->coder, 0, V->lv0, 32, 0);
-  LANE0 { S->h64[i].cy = cy; S->h64[i].ssd_y = V->red[0]; S->h64[i].bits_y = by; }
+  SERIAL { S->h64[i].cy = cy; S->h64[i].ssd_y = V->red[0]; S->h64[i].bits_y = by; }
   CTU_SYNC();
 }
 // a chroma block of transform unit i (depth 2's wave: a 16x16 block is that depth's luma size, so the levels of Cb and Cr take turns
@@ -3236,7 +2837,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void chroma64_step(lds<PX> *S, const
   const int cu = color == 2 ? S->h64[i].cu : 0;
   const int has = recon_tu64(S, J, color, i, S->m64[1], cu, V->lv0);
   const double cb = coeff_bits(S, S->coder, 0, V->lv0, 16, color);
-  LANE0 {
+  SERIAL {
     if (color == 1) { S->h64[i].cu = has; S->h64[i].ssd_u = V->red[1]; S->h64[i].bits = cb; }
     else {
       double fb = 0;
@@ -3256,7 +2857,7 @@ template <typename PX> CTU_DEV void post64(lds<PX> *S, const job<PX> &J)
   SERIAL { S->m64[0] = cu_at(S, 0, 0)->mode; S->m64[1] = cu_at(S, 0, 0)->mode_chroma; }
   CTU_SYNC();
 #if defined(__HIPCC__)
-  LANE0 mb_store(&S->req64, 1);
+  SERIAL mb_store(&S->req64, 1);
 #else
   const int me = g_emul_wave;           // host emulation: the other waves' work happens right here
   S->req64 = 1;
@@ -3300,7 +2901,7 @@ template <typename PX> CTU_DEV bool finish64(lds<PX> *S, const job<PX> &J)
   CTU_T1(J.W, 12); }        // (profile slots 12 / 13 of the walk's wave: the wait for the two chains, unpark64)
 #endif
   CTU_SYNC();
-  LANE0 {
+  SERIAL {
     // the models are the CTU's entry models (the coder's, untouched until its pass after the search) and do not adapt
     // (search_cabac.update is 0 on this path): bits only
     const int mode = S->m64[0], mode_chroma = S->m64[1];
@@ -3350,7 +2951,7 @@ template <typename PX> CTU_DEV void post_eval(lds<PX> *S, const job<PX> &J, int 
 {
 #if defined(__HIPCC__)
   CTU_SYNC();
-  LANE0 mb_store(&S->req[L], S->req[L] + 1);
+  SERIAL mb_store(&S->req[L], S->req[L] + 1);
 #else
   const int me = g_emul_wave;
   g_emul_wave = 4 - L;                  // host emulation: the other wave's work happens right here
@@ -3401,7 +3002,7 @@ template <typename PX> CTU_DEV void worker_loop(lds<PX> *S, const job<PX> &J)
         coder_pass(S, J, L == 3 ? CODER_FLAGS : CODER_CHROMA);
         CTU_T1(J.W, 8); }
         CTU_SYNC();
-        LANE0 mb_store(&S->cdone[3 - L], 1);
+        SERIAL mb_store(&S->cdone[3 - L], 1);
         coded = true;
         continue;
       }
@@ -3412,14 +3013,14 @@ template <typename PX> CTU_DEV void worker_loop(lds<PX> *S, const job<PX> &J)
       seen = r;
       eval_cu(S, J, L, 1);
       CTU_SYNC();
-      LANE0 mb_store(&S->done[L], r);
+      SERIAL mb_store(&S->done[L], r);
     } else if (step) {
       if (L == 1) luma64_step(S, J, n64); else chroma64_step(S, J, n64 >> 1, 1 + (n64 & 1));
-      if (++n64 == steps64) { CTU_SYNC(); LANE0 mb_store(&S->done64[L - 1], 1); }
+      if (++n64 == steps64) { CTU_SYNC(); SERIAL mb_store(&S->done64[L - 1], 1); }
     } else {
       hseen = h;
       help_run(S, J);
-      LANE0 mb_store(&S->hdone, h);
+      SERIAL mb_store(&S->hdone, h);
     }
   }
 }
@@ -3453,13 +3054,13 @@ template <typename PX> CTU_DEV void search_ctu(lds<PX> *S, const job<PX> &J)
         // a leaf: evaluated here, straight into the decided state
         if (can_intra) {
           CTU_T0();
-          LANE0 S->vsel[CTU_WAVE] = 4 - L;          // the scratch sized for this depth (its own wave has nothing to do for a leaf)
+          SERIAL S->vsel[CTU_WAVE] = 4 - L;          // the scratch sized for this depth (its own wave has nothing to do for a leaf)
           CTU_SYNC();
-#if defined(CTU_LEAF4)
+#if defined(__HIPCC__)
           if (L == 4) eval_cu4(S, J); else
 #endif
           eval_cu(S, J, L, 0);
-          LANE0 S->vsel[CTU_WAVE] = 0;
+          SERIAL S->vsel[CTU_WAVE] = 0;
           CTU_SYNC();
           CTU_T1(J.W, 19 + L);
         }
@@ -3467,7 +3068,7 @@ template <typename PX> CTU_DEV void search_ctu(lds<PX> *S, const job<PX> &J)
         ret = N.cost; entering = 0; if (L == 0) break; --L; continue;
       }
       SERIAL { N.type = can_intra ? CU_INTRA : CU_NOTSET; N.cost = CTU_MAX_DOUBLE; N.pending = can_intra; }
-#if defined(CTU_LEAF4)
+#if defined(__HIPCC__)
       if (n == 8) leaf_load_area(S, J, x & 63, y & 63);          // (the 8x8 CU's chroma blocks and the four 4x4 CUs below it read the source from there)
 #endif
       if (can_intra) { copy_models(S->work[L - 1], S->cur); post_eval(S, J, L); }          // its own wave evaluates the CU unsplit from these models ...
@@ -3556,7 +3157,7 @@ CTU_DEV int z_to_x(int z) { return (z & 1) | ((z >> 1) & 2) | ((z >> 2) & 4) | (
 // last position / group flags of colour type 0) and the chroma coefficients (the same of colour type 1, Cb before Cr).  Three waves
 // run them side by side (run_ctu); the host emulation runs them one after the other.  (enum CODER_*: above worker_loop)
 
-#if defined(CTU_LEAF4)
+#if defined(__HIPCC__)
 // the real coder's walk over an 8x8 area of four 4x4 CUs (the shape most of a detailed CTU consists of): the area's 64 + 32 levels are
 // fetched once, a lane each; every block's bins go through coeff_bits4r from registers.  Same bins in the same order as coder_pass.
 template <typename PX> CTU_DEV void coder_area4(lds<PX> *S, const job<PX> &J, int lx, int ly, int parts)
@@ -3584,7 +3185,7 @@ template <typename PX> CTU_DEV void coder_area4(lds<PX> *S, const job<PX> &J, in
         if (a && a->type == CU_INTRA && y % LCU != 0) above_dir = a->mode;
         lf_mpm(__builtin_amdgcn_readfirstlane(left_dir), __builtin_amdgcn_readfirstlane(above_dir), mpm);
       }
-      LANE0 {
+      SERIAL {
         double dummy = 0;
         if (k == 0)          // split flags of the enclosing quad-tree nodes that begin here (a 4x4 CU has none of its own)
           for (int d = 0; (64 >> d) > 4; ++d) {
@@ -3594,7 +3195,7 @@ template <typename PX> CTU_DEV void coder_area4(lds<PX> *S, const job<PX> &J, in
         lf_luma_mode_bits(S->coder, mpm, mode, dummy);
         m_code(m, 1, M_CBF_LUMA + 0, cb_y, dummy);
       }
-      WSYNC();
+      CTU_SYNC();
     }
     if ((parts & CODER_LUMA) && cb_y) (void)coeff_bits4r<PX, false>(S, m, 1, lf_shfl(lev_all, k * 16 + r), 0);
     if (k == 3) {
@@ -3602,13 +3203,13 @@ template <typename PX> CTU_DEV void coder_area4(lds<PX> *S, const job<PX> &J, in
       const cu4 *a = cu_at(S, lx, ly);
       const int acbf = __builtin_amdgcn_readfirstlane((int)a->cbf), au = (acbf >> 1) & 1, av = (acbf >> 2) & 1;
       if (parts & CODER_FLAGS) {
-        LANE0 {
+        SERIAL {
           double dummy = 0;
           chroma_mode_bits(S->coder, 1, c->mode_chroma, c->mode, dummy);
           m_code(m, 1, M_CBF_CB + 0, au, dummy);
           m_code(m, 1, M_CBF_CR + au, av, dummy);
         }
-        WSYNC();
+        CTU_SYNC();
       }
       if (parts & CODER_CHROMA) {
         if (au) (void)coeff_bits4r<PX, false>(S, m, 1, lf_shfl(clev, r), 1);
@@ -3633,7 +3234,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void coder_pass(lds<PX> *S, const jo
     const cu4 *c = cu_at(S, lx, ly);
     const int n = 1 << c->log2;
     if ((lx & (n - 1)) || (ly & (n - 1))) continue;
-#if defined(CTU_LEAF4)
+#if defined(__HIPCC__)
     if (n == 4) {              // (4x4 CUs come as whole 8x8 areas, the first of the four at the area's origin)
       if (!(lx & 4) && !(ly & 4)) coder_area4(S, J, lx, ly, parts);
       continue;
@@ -3653,7 +3254,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void coder_pass(lds<PX> *S, const jo
       const int au = sep ? (a->cbf >> 1) & 1 : cb_u, av = sep ? (a->cbf >> 2) & 1 : cb_v;
       uint32_t *m = S->coder;
       if (parts & CODER_FLAGS) {
-        LANE0 {
+        SERIAL {
           double dummy = 0;
           if (tu == 0) {
             // split flags of the enclosing quad-tree nodes that begin here, then this CU's own
@@ -3677,7 +3278,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void coder_pass(lds<PX> *S, const jo
             m_code(m, 1, M_CBF_CR + au, av, dummy);
           }
         }
-        WSYNC();
+        CTU_SYNC();
       }
       if ((parts & CODER_LUMA) && cb_y) {
         const int16_t *co = J.coeff + tly * LCU + tlx;
@@ -3855,7 +3456,7 @@ template <typename PX> CTU_DEV void setup_waves(lds<PX> *S, scratch *W = nullptr
     else { V->lv0 = (int16_t *)a; V->lv1 = V->lv0 + nn; V->lv2 = V->lv1 + c2; a += (nn + 2 * c2) * 2; }
     // the rough search's (satd, sad) per (mode, tile) -- 2 * 18 * tiles words -- fit the three transform buffers from 8x8 on, which
     // idle until the mode is chosen
-#if defined(CTU_LEAF4)
+#if defined(__HIPCC__)
     if (n == 4) { V->part = nullptr; V->rq_cc = V->rq_cs = nullptr; }       // (the general evaluation never runs on this scratch: eval_cu4)
     else
 #endif
@@ -3880,15 +3481,11 @@ template <typename PX> CTU_DEV void setup_waves(lds<PX> *S, scratch *W = nullptr
 // one CTU, start to finish (all four waves)
 template <typename PX> CTU_DEV void run_ctu(lds<PX> *S, const job<PX> &J)
 {
-#if defined(__HIPCC__) && defined(CTU_PROFILE)
-  BLK_FOR(i, 4 * 32) J.W->prof[i >> 5][i & 31] = 0;
-  BLK_FOR(i, 16) J.W->prof_lf[i] = 0;
-  S->prof_w = J.W;
-#endif
+  CTU_PROF_RESET(S, J)
   CTU_T0();
   { CTU_T0();
   setup_waves(S, J.W);
-#if defined(CTU_LEAF4)
+#if defined(__HIPCC__)
   leaf_tables(S, J.P);
 #endif
   if (CTU_WAVE == 0) build_scans(S);
@@ -3905,12 +3502,12 @@ template <typename PX> CTU_DEV void run_ctu(lds<PX> *S, const job<PX> &J)
     search_ctu(S, J);
     PAR_FOR(i, NMODELS) J.models_out[NMODELS + i] = S->cur[i];
     { CTU_T0();
-    LANE0 S->vsel[CTU_WAVE] = 3;          // the depth-1 scratch for the coder's 32x32 blocks: the other waves are idle now
+    SERIAL S->vsel[CTU_WAVE] = 3;          // the depth-1 scratch for the coder's 32x32 blocks: the other waves are idle now
     CTU_SYNC();
 #if defined(__HIPCC__)
     // the coder's pass, split by model (CODER_*): the flags on depth 3's wave, the chroma coefficients on depth 2's, the luma
     // coefficients here
-    LANE0 mb_store(&S->creq, 1);
+    SERIAL mb_store(&S->creq, 1);
     { CTU_T0();
     coder_pass(S, J, CODER_LUMA);
     CTU_T1(J.W, 14); }        // (profile slot 14 of the walk's wave: its own part; slot 8: with the wait for the other two)
@@ -3918,12 +3515,12 @@ template <typename PX> CTU_DEV void run_ctu(lds<PX> *S, const job<PX> &J)
     CTU_SYNC();
 #else
     coder_pass(S, J, CODER_LUMA);
-    LANE0 S->vsel[CTU_WAVE] = 0;
+    SERIAL S->vsel[CTU_WAVE] = 0;
     { const int me = g_emul_wave; g_emul_wave = 1; coder_pass(S, J, CODER_FLAGS); g_emul_wave = 2; coder_pass(S, J, CODER_CHROMA); g_emul_wave = me; }
 #endif
     CTU_T1(J.W, 8); }
 #if defined(__HIPCC__)
-    LANE0 { for (int L = 1; L <= 3; ++L) mb_store(&S->req[L], -1); }
+    SERIAL { for (int L = 1; L <= 3; ++L) mb_store(&S->req[L], -1); }
   } else {
     worker_loop(S, J);
   }

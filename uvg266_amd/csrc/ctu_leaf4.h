@@ -27,11 +27,7 @@
 
 CTU_DEV int lf_shfl(int v, int src_lane) { return __builtin_amdgcn_ds_bpermute(src_lane << 2, v); }
 // the value of lane + OFF of the same row of 16 lanes (0 beyond the row)
-#if defined(LEAF_NO_DPP)
-template <int OFF> CTU_DEV int lf_nb(int v) { const int l = (int)(threadIdx.x & 63); const int o = lf_shfl(v, l + OFF); return ((l & 15) + OFF) < 16 ? o : 0; }
-#else
 template <int OFF> CTU_DEV int lf_nb(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x100 + OFF, 0xf, 0xf, true); }      // row_shl:OFF
-#endif
 // sum over the 16 lanes of a row, valid in every lane of the row
 CTU_DEV int lf_row_sum(int v)
 {
@@ -85,7 +81,7 @@ template <typename PX> CTU_DEV void leaf_load_area(lds<PX> *S, const job<PX> &J,
     dst[l] = v;
     if (l < 32) dst[64 + l] = c;
   }
-  LANE0 S->lf_tag = tag;
+  SERIAL S->lf_tag = tag;
   CTU_SYNC();
 }
 // lane e (0..15; the lanes above repeat) -> source sample e of the 4x4 block of `color` at CTU-local luma (lx, ly)
@@ -294,8 +290,8 @@ CTU_DEV void lf_luma_mode_bits(uint32_t *m_, const int (&p)[6], int mode, double
 }
 
 // ---- coefficient bit cost of a 4x4 block -------------------------------------------------------------------------------------------
-// coeff_bits4 (ctu_core.h) with the block in RASTER order over the lanes 0..15 (`lev`: the signed level of position lane & 15; every
-// row of 16 lanes may repeat it): the context template's neighbours are DPP row shifts, what is counted along the scan reads the
+// coeff_bits (ctu_core.h) for the one coefficient group of a 4x4 block, in RASTER order over the lanes 0..15 (`lev`: the signed level
+// of position lane & 15; every row of 16 lanes may repeat it): the context template's neighbours are DPP row shifts, what is counted along the scan reads the
 // owners' registers in scan order, and the entropy-table lookups are taken out of the adaptation chain (a model's state after a bin
 // does not depend on the bin's cost): the sixteen steps of the sweep are pure register arithmetic, the sixteen lookups go out together.
 // Same bins, same adaptation, same sum as uvg_encode_coeff_nxn in count mode (encode_coding_tree-generic.c:53-323).
@@ -403,7 +399,7 @@ template <typename PX, bool BITS = true> CTU_DEV double coeff_bits4r(lds<PX> *S,
     if (pbin) { s0 += (0x7fffu >> p0w) & 0x7fe0u; s1 += (0x7fffu >> p1w) & 0x7ffeu; }
     if (phit && update) m[pmodel] = (s0 & 0xffffu) | (s1 << 16);
   }
-  if (!BITS) { WSYNC(); return 0.0; }
+  if (!BITS) { CTU_SYNC(); return 0.0; }
   // ---- the bins' costs, all lookups in flight together ----
   CTU_LDS const uint32_t *const ebits = LDSP(const uint32_t, tab_ebits());
   uint32_t acc = 0;
@@ -430,7 +426,7 @@ template <typename PX, bool BITS = true> CTU_DEV double coeff_bits4r(lds<PX> *S,
   const unsigned q15 = (unsigned)__builtin_amdgcn_readlane(racc, 0) + (unsigned)__builtin_amdgcn_readlane(racc, 16) + (unsigned)__builtin_amdgcn_readlane(racc, 32) +
                        (unsigned)__builtin_amdgcn_readlane(racc, 48);
   const int ib = __builtin_amdgcn_readlane(lf_row_sum(ibits), 0);
-  WSYNC();
+  CTU_SYNC();
   return (double)q15 / 32768.0 + (double)ib;
 }
 

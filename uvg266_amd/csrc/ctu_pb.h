@@ -30,17 +30,7 @@
 #include "satd_tile_dev.h"
 #endif
 
-#if defined(__HIPCC__) && defined(CTU_PROFILE)
-#define PB_T0() const unsigned long long pb_t0__ = __builtin_amdgcn_s_memtime()
-#if defined(CTU_PROFILE_WALK)      // only the walk's wave counts the phases of eval_pb (slots < 14): they add up to its time
-#define PB_T1(W, slot) do { if (CTU_TID == 0 && ((slot) >= 14 || CTU_WAVE == 0)) (W)->prof_pb[slot] += __builtin_amdgcn_s_memtime() - pb_t0__; } while (0)
-#else
-#define PB_T1(W, slot) do { if (CTU_TID == 0) (W)->prof_pb[slot] += __builtin_amdgcn_s_memtime() - pb_t0__; } while (0)
-#endif
-#else
-#define PB_T0() ((void)0)
-#define PB_T1(W, slot) ((void)0)
-#endif
+// (PB_T0 / PB_T1, the phase timers of a CTU_PROFILE build: with the other timer macros at the top of ctu_core.h)
 // prof_pb slots: 0 candidate lists, 1 merge analysis (prediction + SATD), 2 early skip test, 3 integer motion search, 4 fractional search,
 // 5 bi-prediction, 6 intra rough search + chroma trial, 7 the inter CU's prediction + residual, 8 its bits + cost, 9 the intra CU (eval_cu),
 // 10 unpark / 64x64 save + restore, 11 load, 12 store + deblock side effect, 13 coder pass, 14 total, 15 4x4 leaves
@@ -1223,7 +1213,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void finish_inter(lds<PX> *S, const 
     ssd_block(S, J, 1, (lx + ox), (ly + oy), q, 1, T.ru + (oy >> 1) * T.rpc + (ox >> 1), T.rpc);
     ssd_block(S, J, 2, (lx + ox), (ly + oy), q, 2, T.rv + (oy >> 1) * T.rpc + (ox >> 1), T.rpc);
     double luma_bits = 0, chroma_bits = 0, coeff_bits_ = 0;
-    LANE0 {
+    SERIAL {
       CTU_LDS uint32_t *const m = LDSP(uint32_t, V->cur);
       if (!cu.merged) m_code(m, 1, M_ROOT_CBF, (cbf & 7) != 0, luma_bits);
       if (!skip_residual) {
@@ -1232,7 +1222,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void finish_inter(lds<PX> *S, const 
       }
       if ((cb_u || cb_v) && !skip_residual) m_code(m, 1, M_CBF_LUMA + 0, cb_y, luma_bits);
     }
-    WSYNC();
+    CTU_SYNC();
     const unsigned luma_ssd = (unsigned)V->red[0];
     if (cb_y) coeff_bits_ += coeff_bits(S, V->cur, 1, lv_of(V, 0), q, 0);
     const unsigned ssd_u = (unsigned)((unsigned)V->red[1] * P.chroma_weight_u), ssd_v = (unsigned)((unsigned)V->red[2] * P.chroma_weight_v);
@@ -1267,10 +1257,10 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_pb(lds<PX> *S, const job<P
   pb_state &Q = pbq(S);
   level_state &N = S->lvl[L];
   const int n = 64 >> L, x = N.x, y = N.y, lx = x & 63, ly = y & 63;
-  LANE0 S->vsel[CTU_WAVE] = L == 0 ? 3 : 4 - L;
+  SERIAL S->vsel[CTU_WAVE] = L == 0 ? 3 : 4 - L;
   CTU_SYNC();
   wctx *const V = wv_of(S);
-  LANE0 { V->cur = L == 0 ? S->pb.work0 : S->work[L - 1]; Q.hm = S->pb.hmvp_entry[L]; }
+  SERIAL { V->cur = L == 0 ? S->pb.work0 : S->work[L - 1]; Q.hm = S->pb.hmvp_entry[L]; }
   CTU_SYNC();
   const cu_target<PX> T = target_of(S, J, L);
   double cost = CTU_MAX_DOUBLE;
@@ -1296,7 +1286,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_pb(lds<PX> *S, const job<P
       ssd_block(S, J, 1, lx, ly, n, 1, T.ru, T.rpc);
       ssd_block(S, J, 2, lx, ly, n, 2, T.rv, T.rpc);
       double tr_tree_bits = 0, cbits = 0;
-      LANE0 {
+      SERIAL {
         CTU_LDS const uint32_t *const m = LDSP(const uint32_t, V->cur);
         tr_tree_bits += m_fbits(m, M_CBF_CB + 0, cu_);
         tr_tree_bits += m_fbits(m, M_CBF_CR + cu_, cv_);
@@ -1324,7 +1314,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_pb(lds<PX> *S, const job<P
     SERIAL { N.cost = CTU_MAX_DOUBLE; N.type = CU_NOTSET; }
     CTU_SYNC();
   }
-  LANE0 S->vsel[CTU_WAVE] = 0;
+  SERIAL S->vsel[CTU_WAVE] = 0;
   CTU_SYNC();
 }
 
@@ -1437,7 +1427,7 @@ template <typename PX> CTU_DEV void leaves_run(lds<PX> *S, const job<PX> &J)    
 {
   const params &P = J.P;
   for (int k = 0; k < 4; ++k) {
-    LANE0 {
+    SERIAL {
       level_state &C = S->lvl[4];
       const level_state &N = S->lvl[3];
       C.x = N.x + (k & 1) * 4; C.y = N.y + (k >> 1) * 4; C.has_chroma = k == 3;
@@ -1449,19 +1439,19 @@ template <typename PX> CTU_DEV void leaves_run(lds<PX> *S, const job<PX> &J)    
       double sum = 0;
       for (int j = 0; j < k; ++j) sum += S->leaf_cost[j];
       const double lim = __hip_atomic_load(&S->leaf_limit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      if (sum > lim) { LANE0 { for (int j = k; j < 4; ++j) S->leaf_cost[j] = CTU_MAX_DOUBLE; } CTU_SYNC(); break; }
+      if (sum > lim) { SERIAL { for (int j = k; j < 4; ++j) S->leaf_cost[j] = CTU_MAX_DOUBLE; } CTU_SYNC(); break; }
     }
 #endif
     const level_state &C = S->lvl[4];
     const int mode_type_parent = (int)((C.mode_type_tree >> (3 * 2)) & 3);
     const int can_intra = mode_type_parent != 1 && P.depth_max >= 4;          // (an 8x8 area of a picture whose sides are multiples of 8 lies inside it)
-#if defined(CTU_LEAF4)
-    if (can_intra) { PB_T0(); eval_cu4(S, J); PB_T1(J.W, 15); }          // the register-resident 4x4 CU of ctu_leaf4.h (device builds)
+#if defined(__HIPCC__)
+    if (can_intra) { PB_T0(); eval_cu4(S, J); PB_T1(J.W, 15); }          // the register-resident 4x4 CU of ctu_leaf4.h
 #else
     if (can_intra) { PB_T0(); eval_cu(S, J, 4, 0); PB_T1(J.W, 15); }
 #endif
     else { SERIAL { S->lvl[4].cost = CTU_MAX_DOUBLE; S->lvl[4].type = CU_NOTSET; } CTU_SYNC(); }
-    LANE0 S->leaf_cost[k] = S->lvl[4].cost;
+    SERIAL S->leaf_cost[k] = S->lvl[4].cost;
     CTU_SYNC();
   }
 }
@@ -1469,7 +1459,7 @@ template <typename PX> CTU_DEV void post_leaves(lds<PX> *S, const job<PX> &J)
 {
 #if defined(__HIPCC__)
   CTU_SYNC();
-  LANE0 mb_store(&S->req[0], S->req[0] + 1);
+  SERIAL mb_store(&S->req[0], S->req[0] + 1);
 #else
   const int me = g_emul_wave;
   g_emul_wave = 1;                      // host emulation: the leaf wave's work happens right here
@@ -1498,7 +1488,7 @@ template <typename PX> CTU_DEV void leaf_worker_loop(lds<PX> *S, const job<PX> &
     leaves_run(S, J);
     PB_T1(J.W, 21); }
     CTU_SYNC();
-    LANE0 mb_store(&S->done[0], r);
+    SERIAL mb_store(&S->done[0], r);
   }
 }
 #endif
@@ -1517,7 +1507,7 @@ template <typename PX> CTU_DEV void post_eval_pb(lds<PX> *S, const job<PX> &J, i
 {
 #if defined(__HIPCC__)
   CTU_SYNC();
-  LANE0 mb_store(&S->req[mb_of(L)], S->req[mb_of(L)] + 1);
+  SERIAL mb_store(&S->req[mb_of(L)], S->req[mb_of(L)] + 1);
 #else
   const int me = g_emul_wave;
   g_emul_wave = S->depth_wave == 2 && L <= 1 ? 3 : 2;                      // host emulation: the depth wave's work happens right here
@@ -1562,7 +1552,7 @@ template <typename PX> CTU_DEV void depth_worker_loop(lds<PX> *S, const job<PX> 
     if (!mb_load(&S->skip_eval[mb_of(L)])) eval_pb(S, J, L, S->lvl[L].can & 1, S->lvl[L].can >> 1);
     PB_T1(J.W, L == 2 ? 19 : (L == 1 ? 20 : 22)); }
     CTU_SYNC();
-    LANE0 mb_store(&S->done[mb_of(L)], r);
+    SERIAL mb_store(&S->done[mb_of(L)], r);
   }
 }
 #endif
@@ -1618,16 +1608,14 @@ template <typename PX> CTU_DEV void search_ctu_pb(lds<PX> *S, const job<PX> &J)
           for (int a = A + 1; a < L; ++a)
             if (S->lvl[a].evalp && !S->lvl[a].known) {          // an evaluation of a node in between is still out: not wanted, but its buffers are in use
 #if defined(__HIPCC__)
-              LANE0 mb_store(&S->skip_eval[mb_of(a)], 1);
+              SERIAL mb_store(&S->skip_eval[mb_of(a)], 1);
               wait_eval_pb(S, a);
-              LANE0 mb_store(&S->skip_eval[mb_of(a)], 0);
+              SERIAL mb_store(&S->skip_eval[mb_of(a)], 0);
               CTU_SYNC();
 #endif
             }
           L = A;
-#if defined(__HIPCC__) && defined(CTU_PROFILE)
-          LANE0 J.W->prof_pb[18] += 1;
-#endif
+          PB_COUNT(J.W, 18)
           level_state &M = S->lvl[L];
           const int ntype = M.type;
           CTU_SYNC();
@@ -1653,7 +1641,7 @@ template <typename PX> CTU_DEV void search_ctu_pb(lds<PX> *S, const job<PX> &J)
         // a 4x4 CU: intra only, nothing to split, no history entry
         if (can_intra) {
           PB_T0();
-#if defined(CTU_LEAF4)
+#if defined(__HIPCC__)
           eval_cu4(S, J);
 #else
           eval_cu(S, J, L, 0);
@@ -1711,12 +1699,12 @@ template <typename PX> CTU_DEV void search_ctu_pb(lds<PX> *S, const job<PX> &J)
           C.split_tree = N.split_tree | 1u << (L * 3);
           C.mode_type_tree = N.mode_type_tree | mode_type << (L * 2);
         }
-        LANE0 S->leaf_limit = CTU_MAX_DOUBLE;
+        SERIAL S->leaf_limit = CTU_MAX_DOUBLE;
         post_leaves(S, J);
         if (will_eval) { PB_T0(); eval_pb(S, J, L, can_inter, can_intra); PB_T1(J.W, 23); }
 #if defined(__HIPCC__)
         // the CU's cost is in: what the split may cost at most before it has lost (pruned: nothing) -- the leaf wave stops there
-        LANE0 {
+        SERIAL {
           const double factor = P.qp > 30 ? 1.1 : 1.075;
           const bool pruned = N.split_bits * P.lambda + N.cost / factor > N.cost;
           __hip_atomic_store(&S->leaf_limit, pruned ? -1.0 : N.cost - N.split_bits * P.lambda, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -2004,7 +1992,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void coder_pass_pb(lds<PX> *S, const
     const int skipped = is_inter && S->pb.fl[u0][0];
     CTU_SYNC();
     // ---- the CU's header ----
-    LANE0 {
+    SERIAL {
       CTU_LDS uint32_t *const m = LDSP(uint32_t, S->coder);
       double dummy = 0;
       for (int d = 0; (64 >> d) > n; ++d) {
@@ -2061,7 +2049,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void coder_pass_pb(lds<PX> *S, const
         uint32_t *m = S->coder;
         double dummy = 0;
         const int cb_y = t->cbf & 1, cb_u = (t->cbf >> 1) & 1, cb_v = (t->cbf >> 2) & 1;
-        LANE0 {
+        SERIAL {
           if (!sep) {
             m_code(m, 1, M_CBF_CB + 0, cb_u, dummy);
             m_code(m, 1, M_CBF_CR + cb_u, cb_v, dummy);
@@ -2069,7 +2057,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void coder_pass_pb(lds<PX> *S, const
           // encode_transform_coeff :700-716: an inter CU that is one transform unit with no chroma residual implies its luma flag
           if (!is_inter || n == 64 || cb_u || cb_v) m_code(m, 1, M_CBF_LUMA + 0, cb_y, dummy);
         }
-        WSYNC();
+        CTU_SYNC();
         if (cb_y) (void)coeff_bits(S, m, 1, lv_of(V, 0), tn, 0);
         if (!sep) {
           if (cb_u) (void)coeff_bits(S, m, 1, lv_of(V, 1), tn >> 1, 1);
@@ -2077,12 +2065,12 @@ template <typename PX> CTU_NOINLINE CTU_DEV void coder_pass_pb(lds<PX> *S, const
         } else if (last4) {
           const cu4 *a = cu_at(S, lx & ~7, ly & ~7);
           const int au = (a->cbf >> 1) & 1, av = (a->cbf >> 2) & 1;
-          LANE0 {
+          SERIAL {
             chroma_mode_bits(m, 1, c->mode_chroma, c->mode, dummy);
             m_code(m, 1, M_CBF_CB + 0, au, dummy);
             m_code(m, 1, M_CBF_CR + au, av, dummy);
           }
-          WSYNC();
+          CTU_SYNC();
           if (au) (void)coeff_bits(S, m, 1, lv_of(V, 1), 4, 1);
           if (av) (void)coeff_bits(S, m, 1, lv_of(V, 2), 4, 2);
         }
@@ -2095,17 +2083,13 @@ template <typename PX> CTU_NOINLINE CTU_DEV void coder_pass_pb(lds<PX> *S, const
 // one CTU of a P / B picture, start to finish (one wave)
 template <typename PX> CTU_DEV void run_ctu_pb(lds<PX> *S, const job<PX> &J)
 {
-#if defined(__HIPCC__) && defined(CTU_PROFILE)
-  BLK_FOR(i, 24) J.W->prof_pb[i] = 0;
-  BLK_FOR(i, 4 * 32) J.W->prof[i >> 5][i & 31] = 0;
-  S->prof_w = J.W;
-#endif
+  PB_PROF_RESET(S, J)
   PB_T0();
   { PB_T0();
   static_assert(sizeof(icand::unit) == 32, "scratch::pb_mot holds icand::unit as eight int32");
   if (BLK_TID == 0) { S->pb.mot = reinterpret_cast<icand::unit *>(J.W->pb_mot); S->pb.fl = J.W->pb_fl; }
   setup_waves(S, J.W);
-#if defined(CTU_LEAF4)
+#if defined(__HIPCC__)
   leaf_tables(S, J.P);
 #endif
   BLK_FOR(k, 4) S->wv[k].rq_root = 0;
@@ -2137,7 +2121,7 @@ template <typename PX> CTU_DEV void run_ctu_pb(lds<PX> *S, const job<PX> &J)
     PAR_FOR(i, NMODELS) J.models_out[NMODELS + i] = S->cur[i];
     PAR_FOR(i, NMX - NMODELS) J.pbm_out[(NMX - NMODELS) + i] = S->cur[NMODELS + i];
 #if defined(__HIPCC__)
-    LANE0 { if (S->leaf_wave) mb_store(&S->req[0], -1); if (S->depth_wave) mb_store(&S->req[1], -1); }
+    SERIAL { if (S->leaf_wave) mb_store(&S->req[0], -1); if (S->depth_wave) mb_store(&S->req[1], -1); }
   } else if (CTU_WAVE == 1) leaf_worker_loop(S, J);
   else depth_worker_loop(S, J);
 #endif
@@ -2148,12 +2132,12 @@ template <typename PX> CTU_DEV void run_ctu_pb(lds<PX> *S, const job<PX> &J)
   deblock_zeroes_unused_vectors(S, J);
   PB_T1(J.W, 12); }
   if (CTU_WAVE == 0) {
-    LANE0 S->vsel[CTU_WAVE] = 3;
+    SERIAL S->vsel[CTU_WAVE] = 3;
     CTU_SYNC();
     { PB_T0();
     coder_pass_pb(S, J);
     PB_T1(J.W, 13); }
-    LANE0 S->vsel[CTU_WAVE] = 0;
+    SERIAL S->vsel[CTU_WAVE] = 0;
   }
   BLK_SYNC();
   BLK_FOR(i, NMODELS) J.models_out[2 * NMODELS + i] = S->coder[i];
