@@ -29,9 +29,8 @@ print("%-28s %12s %12s %12s %12s" % ("", "wave0 (4x4+walk)", "wave1 (8x8)", "wav
 for i, nm in enumerate(names):
     print("  %-26s" % nm + "".join("%12.0f" % prof[:, w, i].mean() for w in range(4)))
 
-print("chroma helper per CTU: Cb blocks handed to depth 3's wave %.1f, kept by the walk (wave busy) %.1f, the walk's wait for them %.0f cycles" % (prof[:, 1, 19].mean(), prof[:, 1, 20].mean(), prof[:, 1, 21].mean()))
 
-lfn = ["area source load", "refs (luma)", "src->sgpr, mpm, planar/DC", "pass A (modes 4..65)", "selection (+ pass B)", "recon: refs (chroma)", "recon: predict + residual + DCT", "recon: RDOQ", "recon: dequant + IDCT + store + SSD", "fill_cu + help + between", "-", "bits: flags + mode bits (lane 0)", "bits: tr_cost (cbf + coeff_bits4)", "bits: cost + deblock marks"]
+lfn = ["area source load", "refs (luma)", "src->sgpr, mpm, planar/DC", "pass A (modes 4..65)", "selection (+ pass B)", "recon: refs (chroma; joint pass: + the luma prediction)", "recon: predict + residual + DCT", "recon: RDOQ", "recon: dequant + IDCT + store + SSD", "fill_cu + between the named steps", "-", "bits: flags + mode bits (lane 0)", "bits: tr_cost (cbf + coeff_bits4)", "bits: cost + deblock marks"]
 print("4x4 leaf, cycles per CTU (walk's wave):")
 for i, nm in enumerate(lfn):
     if nm != "-": print("  %-44s %10.0f   per CU %7.0f" % (nm, lf[:, i].mean(), lf[:, i].mean() / 256))

@@ -57,7 +57,7 @@
 //   CTU_PB        NMX = 257 + 18 models per set; level_state::mot / fl / cbf4; wctx::rq_root; lds::pb .. cur64 (the inter state, the
 //                 leaf and depth waves' own) in place of lds::req64 .. h64 (the 64x64 candidate beside the walk, the coder's pass
 //                 by model); one arena region for the depths 1..3; scratch::save_mot .. prof_pb; job::pb .. init_qp; the extra
-//                 parameter of eval_cu (forced_mode) and of recon_tu / recon_tu_inl (flags); no chroma helper
+//                 parameter of eval_cu (forced_mode) and of recon_tu / recon_tu_inl (flags)
 //   CTU_PROFILE   lds::prof_w in front of the image; on the device the timer macros below count s_memtime ticks into
 //                 scratch::prof / prof_lf / prof_pb (always there; read by slot number by tools/dev/*) -- with CTU_PROFILE_WALK the
 //                 P / B phases of the walk's wave only
@@ -113,8 +113,9 @@
 // The phase timers of a CTU_PROFILE device build: lane 0 of the wave, s_memtime ticks.  No function body tests the switch itself.
 //   CTU_T0 / CTU_T1(W, slot)   a bracketed phase into scratch::prof[wave][slot]; PB_T0 / PB_T1: into scratch::prof_pb[slot]
 //   RQ_T0(W) ... RQ_T(slot)    consecutive phases of one function, each ending at its mark, into scratch::prof[wave][slot]
-//   LF_T0() ... LF_T(slot)     the same for the 4x4 leaf on the walk's wave, into scratch::prof_lf[slot] (`J` in scope)
-//   CTU_HELPED / CTU_TW0 / CTU_TW1, PB_COUNT, CTU_PROF_RESET / PB_PROF_RESET: the counters and the reset that are not a phase
+//   LF_T0() ... LF_T(slot)     the same for the 4x4 leaf on the walk's wave, into scratch::prof_lf[slot] (`J` in scope); LF_TR():
+//                              restart the interval after a step that counted itself
+//   PB_COUNT, CTU_PROF_RESET / PB_PROF_RESET: the counters and the reset that are not a phase
 // RQ_T0 and the last group stand as statements WITHOUT a semicolon of their own: a build without the switch has no token there.
 #if defined(__HIPCC__) && defined(CTU_PROFILE)
 #define CTU_T0() const unsigned long long ctu_t0__ = __builtin_amdgcn_s_memtime()
@@ -123,10 +124,7 @@
 #define RQ_T(slot) do { const unsigned long long t2 = __builtin_amdgcn_s_memtime(); if (CTU_TID == 0) rq_w__->prof[CTU_WAVE][slot] += t2 - tq; tq = t2; } while (0)
 #define LF_T0() unsigned long long tq = __builtin_amdgcn_s_memtime()
 #define LF_T(slot) do { const unsigned long long t2 = __builtin_amdgcn_s_memtime(); if (CTU_TID == 0 && CTU_WAVE == 0) J.W->prof_lf[slot] += t2 - tq; tq = t2; } while (0)
-// the chroma helper (help_post) on depth 3's counters: Cb blocks it took (slot 19) / the walk kept (20), the walk's wait for it (21)
-#define CTU_HELPED(W, on, helped) if (on) { SERIAL (W)->prof[1][(helped) ? 19 : 20] += 1; }
-#define CTU_TW0() const unsigned long long tw = __builtin_amdgcn_s_memtime();
-#define CTU_TW1(W) SERIAL (W)->prof[1][21] += __builtin_amdgcn_s_memtime() - tw;
+#define LF_TR() do { tq = __builtin_amdgcn_s_memtime(); } while (0)          // restart: what ran since the last mark counted itself
 #define CTU_PROF_RESET(S, J) BLK_FOR(i, 4 * 32) (J).W->prof[i >> 5][i & 31] = 0; BLK_FOR(i, 16) (J).W->prof_lf[i] = 0; (S)->prof_w = (J).W;
 #define PB_T0() const unsigned long long pb_t0__ = __builtin_amdgcn_s_memtime()
 #if defined(CTU_PROFILE_WALK)      // only the walk's wave counts the phases of eval_pb (slots < 14): they add up to its time
@@ -143,9 +141,7 @@
 #define RQ_T(slot) ((void)0)
 #define LF_T0() ((void)0)
 #define LF_T(slot) ((void)0)
-#define CTU_HELPED(W, on, helped)
-#define CTU_TW0()
-#define CTU_TW1(W)
+#define LF_TR() ((void)0)
 #define CTU_PROF_RESET(S, J)
 #define PB_T0() ((void)0)
 #define PB_T1(W, slot) ((void)0)
@@ -339,7 +335,7 @@ template <typename PX> struct lds {
   int32_t vsel[4];                                  // which wv[] a wave is using (a wave may borrow a larger one while its owner idles)
   int32_t rot;                                      // index of the wave with role 0 (CTU_WAVE)
   int32_t req[4], done[4];                          // depth pipeline: evaluation requests / completions per depth
-  int32_t hreq, hdone, help[6];                     // the chroma helper (help_post): requests / completions; area x, y, mode -> has_coeffs, SSD
+  int32_t help[4];                                  // the host emulation's chroma helper (help_post): area x, y, mode -> has_coeffs
 #if defined(__HIPCC__)
   // ctu_leaf4.h: the cubic interpolation filter (4 x int8 per phase), intraPredAngle | invAngle << 8 per |mode distance|, per raster
   // position of a 4x4 block (positions later in scan order | scan index << 16 | raster of the next scan index << 20), the 8x8 area
@@ -2291,50 +2287,28 @@ CTU_DEV int mb_load(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_ACQ
 CTU_DEV void mb_store(int32_t *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); }
 #endif
 
-#if !defined(CTU_PB)
-// ---- the chroma helper ------------------------------------------------------------------------------------------------------
+#if !defined(CTU_PB) && !defined(__HIPCC__)
+// ---- the chroma helper (host emulation) ---------------------------------------------------------------------------------------
 // The fourth 4x4 CU of an 8x8 area carries the area's two 4x4 chroma blocks (search.c:355-400).  They depend on that CU's luma MODE
-// only, not on its luma block, and the walk's chain of 4x4 CUs is what a CTU's time is made of: the Cb block goes to the wave of
-// depth 3 -- idle by then, the area's own 8x8 evaluation was posted four CUs ago -- while the walk reconstructs the luma block; Cr
-// follows on the walk (its cbf context wants Cb's flag).  Same arithmetic on the same inputs either way: when the wave is still
-// busy the walk simply does all three blocks itself.
-template <typename PX> CTU_DEV void help_run(lds<PX> *S, const job<PX> &J)          // depth 3's wave
+// only, not on its luma block.  The device reconstructs the three blocks in one pass of the walk's wave (ctu_leaf4.h
+// leaf_recon_rows); the host emulation, which walks a 4x4 CU with the general evaluation, takes both orders: the Cb block on the
+// scratch of depth 3 ahead of the luma block, or all three in turn (g_emul_lazy).  Same arithmetic on the same inputs either way.
+template <typename PX> CTU_DEV void help_run(lds<PX> *S, const job<PX> &J)
 {
-#if defined(__HIPCC__)
-  __builtin_amdgcn_s_setprio(3);                   // the walk waits for this block
-#endif
   const int cx = S->help[0], cy = S->help[1], mode = S->help[2];
   const int lx = cx & 63, ly = cy & 63;
   PX *const ru = S->Du + ((ly >> 1) + 1) * PC + (lx >> 1) + 1;
   int16_t *const ku = J.coeff + 4096 + (ly >> 1) * LCU_C + (lx >> 1);
-#if defined(__HIPCC__)
-  const lf_block B = leaf_recon(S, J, wv_of(S), 1, mode, 0, cx, cy, lx, ly, 8, 0, ru, PC, ku, LCU_C);
-  const int has = B.has;
-  SERIAL S->help[4] = B.ssd;
-#else
   const int has = recon_tu(S, J, 1, cx, cy, lx, ly, 8, mode, 0, ru, PC, ku, LCU_C, 8);
-#endif
   {
-    CTU_LDS const int16_t *const from = LDSP(const int16_t, wv_of(S)->lv1);          // the walk counts the levels' bits from ITS scratch
-    CTU_LDS int16_t *const to = LDSP(int16_t, S->wv[0].lv1);
-    PAR_FOR(e, 16) to[e] = from[e];
+    const int16_t *const from = wv_of(S)->lv1;          // the walk counts the levels' bits from ITS scratch
+    int16_t *const to = S->wv[0].lv1;
+    for (int e = 0; e < 16; ++e) to[e] = from[e];
   }
-  SERIAL S->help[3] = has;
-  CTU_SYNC();
-#if defined(__HIPCC__)
-  __builtin_amdgcn_s_setprio(0);
-#endif
+  S->help[3] = has;
 }
-// the walk: hand the Cb block of the area at (cx, cy) over if depth 3's wave has nothing to do
 template <typename PX> CTU_DEV bool help_post(lds<PX> *S, const job<PX> &J, int cx, int cy, int mode)
 {
-#if defined(__HIPCC__)
-  if (__builtin_amdgcn_readfirstlane(mb_load(&S->done[3]) == S->req[3]) == 0) return false;
-  SERIAL { S->help[0] = cx; S->help[1] = cy; S->help[2] = mode; }
-  CTU_SYNC();
-  SERIAL mb_store(&S->hreq, S->hreq + 1);
-  return true;
-#else
   if (g_emul_lazy) return false;                   // (the host tests take both roads)
   S->help[0] = cx; S->help[1] = cy; S->help[2] = mode;
   const int me = g_emul_wave;
@@ -2342,16 +2316,8 @@ template <typename PX> CTU_DEV bool help_post(lds<PX> *S, const job<PX> &J, int 
   help_run(S, J);
   g_emul_wave = me;
   return true;
-#endif
 }
-template <typename PX> CTU_DEV int help_wait(lds<PX> *S)
-{
-#if defined(__HIPCC__)
-  while (mb_load(&S->hdone) != S->hreq) __builtin_amdgcn_s_sleep(1);
-  CTU_SYNC();
-#endif
-  return S->help[3];
-}
+template <typename PX> CTU_DEV int help_wait(lds<PX> *S) { return S->help[3]; }
 #endif
 
 template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu(lds<PX> *S, const job<PX> &J, int L, int to_cand
@@ -2416,9 +2382,8 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu(lds<PX> *S, const job<P
     rpy = PY; rpc = PC; kpy = LCU; kpc = LCU_C;
   }
   int cbf = 0;
-#if !defined(CTU_PB)
+#if !defined(CTU_PB) && !defined(__HIPCC__)
   const bool helped = sep && has_chroma && !to_cand && help_post(S, J, cx, cy, mode);
-  CTU_HELPED(J.W, sep && has_chroma && !to_cand, helped)
 #else
   const bool helped = false;
 #endif
@@ -2427,23 +2392,22 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu(lds<PX> *S, const job<P
 #endif
   for (int color = 0; color < (has_chroma ? 3 : 1); ++color) {
     const bool c = color != 0;
-#if !defined(CTU_PB)
+#if !defined(CTU_PB) && !defined(__HIPCC__)
     if (helped && color == 1) {
-      CTU_TW0()
       cbf |= help_wait(S) << 1;
-      CTU_TW1(J.W)
       continue;
     }
 #endif
 #if defined(__HIPCC__) && !defined(CTU_PB)
     if (c && n == 8) {
-      // the 4x4 chroma blocks of an 8x8 CU: the register-resident block of ctu_leaf4.h (the area's source samples are in S->lf_src)
+      // the 4x4 chroma blocks of an 8x8 CU: the register-resident blocks of ctu_leaf4.h, Cb and Cr in one pass (the area's source
+      // samples are in S->lf_src; the luma block's reference rows are no longer needed)
       CTU_T0();
-      const lf_block B = leaf_recon(S, J, V, color, mode, color == 2 ? (cbf >> 1) & 1 : 0, x, y, lx, ly, 8, 0, color == 1 ? ru : rv, rpc, color == 1 ? ku : kv, kpc);
-      SERIAL V->red[color] = B.ssd;
-      cbf |= B.has << color;
+      const lf_blocks B = leaf_recon_uv(S, J, V, mode, x, y, lx, ly, ru, rv, rpc, ku, kv, kpc);
+      SERIAL { V->red[1] = B.ssd_u; V->red[2] = B.ssd_v; }
+      cbf |= B.cbf;
       CTU_T1(J.W, 3);
-      continue;
+      break;
     }
 #endif
     const int has = recon_tu_inl(S, J, color, c ? cx : x, c ? cy : y, c ? cx & 63 : lx, c ? cy & 63 : ly, c ? area : n, mode, color == 2 ? (cbf >> 1) & 1 : 0,
@@ -2534,6 +2498,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu4(lds<PX> *S, const job<
   LF_T(1);
   mode = leaf_rough(S, J, V, x, y, lx, ly, leaf_src(S, 0, lx, ly), mpm);
   CTU_T1(J.W, 0); }
+  LF_TR();          // (the rough search and the block passes time themselves: slot 9 is what lies between the named steps)
   SERIAL {          // lcu_fill_cu_info (search.c:314-353) for the one entry of a 4x4 CU
     cu4 *c = cu_at(S, lx, ly);
     c->type = CU_INTRA; c->log2 = 2; c->log2_c = 2; c->mode = (int8_t)mode; c->mode_chroma = (int8_t)mode;
@@ -2550,35 +2515,21 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu4(lds<PX> *S, const job<
   PX *const ru = S->Du + ((cly >> 1) + 1) * PC + (clx >> 1) + 1, *const rv = S->Dv + ((cly >> 1) + 1) * PC + (clx >> 1) + 1;
   int16_t *const ky = J.coeff + ly * LCU + lx;
   int16_t *const ku = J.coeff + 4096 + (cly >> 1) * LCU_C + (clx >> 1), *const kv = J.coeff + 5120 + (cly >> 1) * LCU_C + (clx >> 1);
-#if defined(CTU_PB)
-  const bool helped = false;              // (no chroma helper: the P / B CTU has no depth waves)
-#else
-  const bool helped = has_chroma && help_post(S, J, cx, cy, mode);
-  CTU_HELPED(J.W, has_chroma, helped)
-#endif
+  // the first three CUs of an area: the luma block; the fourth: its luma block and the area's two chroma blocks in one pass, a row of
+  // 16 lanes each (Cb's reference rows in the unused smoothed rows, Cr's in the luma rows once the luma prediction is taken)
   int ssd_y = 0, ssd_u = 0, ssd_v = 0, cbf = 0, lev_y = 0, lev_u = 0, lev_v = 0;
+  LF_T(9);
   { CTU_T0();
-#pragma nounroll
-  for (int color = 0; color < (has_chroma ? 3 : 1); ++color) {          // ONE call site of the block function (see leaf_recon)
-#if !defined(CTU_PB)
-    if (helped && color == 1) {
-      CTU_TW0()
-      cbf |= help_wait(S) << 1;
-      ssd_u = S->help[4];
-      lev_u = (int)LDSP(const int16_t, V->lv1)[CTU_TID & 15];         // (help_run left the levels in the walk's scratch)
-      CTU_TW1(J.W)
-      continue;
-    }
-#endif
-    const bool c = color != 0;
-    const lf_block B = leaf_recon_inl(S, J, V, color, mode, color == 2 ? (cbf >> 1) & 1 : 0, c ? cx : x, c ? cy : y, c ? clx : lx, c ? cly : ly, c ? 8 : 4, c ? 0 : 1,
-                                      color == 0 ? ry : (color == 1 ? ru : rv), c ? PC : PY, color == 0 ? ky : (color == 1 ? ku : kv), c ? LCU_C : LCU);
-    cbf |= B.has << color;
-    if (color == 0) { ssd_y = B.ssd; lev_y = B.level; } else if (color == 1) { ssd_u = B.ssd; lev_u = B.level; } else { ssd_v = B.ssd; lev_v = B.level; }
+  if (has_chroma) {
+    const lf_blocks B = leaf_recon_rows<PX, true>(S, J, V, mode, x, y, lx, ly, cx, cy, clx, cly, V->ftop, V->fleft, V->top, V->left, ry, ru, rv, PY, PC, ky, ku, kv, LCU, LCU_C);
+    cbf = B.cbf; ssd_y = B.ssd_y; ssd_u = B.ssd_u; ssd_v = B.ssd_v; lev_y = B.lev_y; lev_u = B.lev_u; lev_v = B.lev_v;
+  } else {
+    const lf_block B = leaf_recon_inl(S, J, V, 0, mode, 0, x, y, lx, ly, 4, 1, ry, PY, ky, LCU);
+    cbf = B.has; ssd_y = B.ssd; lev_y = B.level;
   }
   CTU_T1(J.W, 3); }
   CTU_T0();
-  LF_T(9);
+  LF_TR();
   // ---- the CU's side information and RD cost (search.c:1700-1774) ----
   double bits = 0;
   SERIAL {
@@ -2982,19 +2933,18 @@ template <typename PX> CTU_DEV void coder_pass(lds<PX> *S, const job<PX> &J, int
 template <typename PX> CTU_DEV void worker_loop(lds<PX> *S, const job<PX> &J)
 {
   const int L = 4 - CTU_WAVE;
-  int seen = 0, hseen = 0;
+  int seen = 0;
   // the 64x64 candidate (post64): depth 1's wave owes it four luma blocks, depth 2's eight chroma blocks, one at a time whenever the
   // wave has no evaluation to do
   const int steps64 = L == 1 ? 4 : (L == 2 ? 8 : 0);
   int n64 = 0;
   bool coded = false;
   for (;;) {
-    int r, h = hseen;
+    int r;
     bool step = false;
     for (;;) {
       r = mb_load(&S->req[L]);
       if (r != seen) break;
-      if (L == 3) { h = mb_load(&S->hreq); if (h != hseen) break; }        // depth 3's wave also takes the walk's Cb blocks (help_post)
       if (n64 < steps64 && mb_load(&S->req64)) { step = true; break; }
       if (L >= 2 && !coded && mb_load(&S->creq)) {
         // the search is over: this wave's part of the coder's pass (depth 3: the flags, depth 2: the chroma coefficients)
@@ -3017,10 +2967,6 @@ template <typename PX> CTU_DEV void worker_loop(lds<PX> *S, const job<PX> &J)
     } else if (step) {
       if (L == 1) luma64_step(S, J, n64); else chroma64_step(S, J, n64 >> 1, 1 + (n64 & 1));
       if (++n64 == steps64) { CTU_SYNC(); SERIAL mb_store(&S->done64[L - 1], 1); }
-    } else {
-      hseen = h;
-      help_run(S, J);
-      SERIAL mb_store(&S->hdone, h);
     }
   }
 }
@@ -3470,7 +3416,6 @@ template <typename PX> CTU_DEV void setup_waves(lds<PX> *S, scratch *W = nullptr
     V->cur = S->cur;
     S->vsel[k] = k;
     S->req[k] = 0; S->done[k] = 0;
-    if (k == 0) { S->hreq = 0; S->hdone = 0; }
 #if !defined(CTU_PB)
     if (k == 0) { S->req64 = 0; S->done64[0] = 0; S->done64[1] = 0; S->creq = 0; S->cdone[0] = 0; S->cdone[1] = 0; }
 #endif

@@ -15,7 +15,9 @@
 //     population count over the positions later in scan order, and the positions are decided together by the fixed-point iteration
 //     of rdoq_wave, which here also covers the blocks where the budget runs out (a position's "regular" flag is a function of the
 //     levels later in scan order, like its contexts: same DAG);  the sums the reference forms in scan order are formed from the
-//     owners' registers with v_readlane in that order.
+//     owners' registers with v_readlane in that order;
+//   * blocks that do not wait for each other -- the Cb and Cr blocks of an 8x8 area and the luma block of the 4x4 CU that carries
+//     them -- go through these steps together, a block per row of 16 lanes (leaf_recon_rows).
 // Device only (the host emulation keeps the general path: the two agree only if this reformulation is right; the GPU tests hold the
 // device to the reference-run goldens).
 // (included by ctu_core.h inside namespace ctu, behind the helpers it builds on)
@@ -95,9 +97,13 @@ template <typename PX> CTU_DEV int leaf_src(lds<PX> *S, int color, int lx, int l
 
 // ---- reference rows ------------------------------------------------------------------------------------------------------------
 // uvg_intra_build_reference (intra.c:756-1341) for a 4x4 block of `color`: the luma block of the 4x4 CU at (lx, ly) (n = 4), or a chroma
-// block of the 8x8 area at (lx, ly) (n = 8).  Entries 0..16 of V->top / V->left (a 4x4 block reads 0..10); no smoothed rows (never used
-// for 4x4 blocks, intra.c:715-725).  Every lane derives the availability itself: no hand-over from lane 0.
-template <typename PX> CTU_DEV void leaf_refs(lds<PX> *S, const params &P, wctx *V, int color, int x, int y, int lx, int ly, int n)
+// block of the 8x8 area at (lx, ly) (n = 8).  Entries 0..16 of top_ / left_ (LDS; a 4x4 block reads 0..10): V->top / V->left unless the
+// caller keeps several blocks' rows side by side; no smoothed rows (never used for 4x4 blocks, intra.c:715-725).  Every lane derives
+// the availability itself: no hand-over from lane 0.
+// UV: both chroma blocks of the area at once -- Cb (color = 1) on the lanes 0..31 into top_ / left_, Cr on the lanes 32..63 into
+// top2_ / left2_ (same availability, same positions, the other plane); the corners follow on the first lane of each half.
+template <typename PX, bool UV = false> CTU_DEV void leaf_refs(lds<PX> *S, const params &P, uint16_t *top_, uint16_t *left_, int color, int x, int y, int lx, int ly, int n,
+                                                               uint16_t *top2_ = nullptr, uint16_t *left2_ = nullptr)
 {
   const int c = color != 0, w = 4;
   const int px_x = lx >> c, px_y = ly >> c, pit = pitch_of(color);
@@ -139,6 +145,25 @@ template <typename PX> CTU_DEV void leaf_refs(lds<PX> *S, const params &P, wctx 
   const int dc = 1 << (px_info<PX>::depth - 1);
   const int l = CTU_TID, i = l & 15;
   int v;
+  if (UV) {
+    const bool second = l >= 32, is_top = (l & 16) != 0;
+    CTU_LDS const PX *const D2 = second ? LDSP(const PX, plane(S, 2)) + (px_y + 1) * pit + px_x + 1 : D;
+    int vc;                   // the corner ("copy reference clockwise": left[1] when the corner itself is missing)
+    if (!is_top) {            // left[1 + i]
+      if (x > 0) v = D2[(i < al ? i : al - 1) * pit - 1];
+      else v = y > 0 ? (int)D2[-pit] : dc;
+    } else {                  // top[1 + i]
+      if (y > 0) v = D2[-pit + (i < at ? i : at - 1)];
+      else v = x > 0 ? (int)D2[-1] : dc;
+    }
+    if (x > 0 && y > 0) vc = D2[-pit - 1];
+    else vc = x > 0 ? (int)D2[-1] : (y > 0 ? (int)D2[-pit] : dc);
+    CTU_LDS uint16_t *const r_top = LDSP(uint16_t, second ? top2_ : top_), *const r_left = LDSP(uint16_t, second ? left2_ : left_);
+    if (is_top) r_top[1 + i] = (uint16_t)v; else r_left[1 + i] = (uint16_t)v;
+    if ((l & 31) == 0) { r_left[0] = (uint16_t)vc; r_top[0] = (uint16_t)vc; }
+    CTU_SYNC();
+    return;
+  }
   if (l < 16) {               // left[1 + i]
     if (x > 0) v = D[(i < al ? i : al - 1) * pit - 1];
     else v = y > 0 ? (int)D[-pit] : dc;
@@ -149,11 +174,15 @@ template <typename PX> CTU_DEV void leaf_refs(lds<PX> *S, const params &P, wctx 
     if (x > 0 && y > 0) v = D[-pit - 1];
     else v = x > 0 ? (int)D[-1] : (y > 0 ? (int)D[-pit] : dc);
   }
-  CTU_LDS uint16_t *const r_top = LDSP(uint16_t, V->top), *const r_left = LDSP(uint16_t, V->left);
+  CTU_LDS uint16_t *const r_top = LDSP(uint16_t, top_), *const r_left = LDSP(uint16_t, left_);
   if (l < 16) r_left[1 + i] = (uint16_t)v;
   else if (l < 32) r_top[1 + i] = (uint16_t)v;
   else if (l == 32) { r_left[0] = (uint16_t)v; r_top[0] = (uint16_t)v; }
   CTU_SYNC();
+}
+template <typename PX> CTU_DEV void leaf_refs(lds<PX> *S, const params &P, wctx *V, int color, int x, int y, int lx, int ly, int n)
+{
+  leaf_refs(S, P, V->top, V->left, color, x, y, lx, ly, n);
 }
 
 // ---- prediction ----------------------------------------------------------------------------------------------------------------
@@ -164,7 +193,7 @@ struct lf_mode {
   int sd, inv;
   bool vertical, pd_ang, pd_sd0;
 };
-template <typename PX> CTU_DEV lf_mode leaf_mode(lds<PX> *S, wctx *V, int mode)
+template <typename PX> CTU_DEV lf_mode leaf_mode(lds<PX> *S, CTU_LDS const uint16_t *top, CTU_LDS const uint16_t *left, int mode)
 {
   lf_mode M;
   M.vertical = mode >= 34;
@@ -174,11 +203,11 @@ template <typename PX> CTU_DEV lf_mode leaf_mode(lds<PX> *S, wctx *V, int mode)
   M.inv = (int)(t >> 8);
   M.pd_ang = md >= 14;
   M.pd_sd0 = md == 0;
-  CTU_LDS const uint16_t *const top = LDSP(const uint16_t, V->top), *const left = LDSP(const uint16_t, V->left);
   M.mainr = M.vertical ? top : left;
   M.side = M.vertical ? left : top;
   return M;
 }
+template <typename PX> CTU_DEV lf_mode leaf_mode(lds<PX> *S, wctx *V, int mode) { return leaf_mode(S, LDSP(const uint16_t, V->top), LDSP(const uint16_t, V->left), mode); }
 // row yd of the WORK domain (the block for vertical modes, its transpose for horizontal ones), 4 samples
 // (intra-generic.c:118-246 for a 4x4 block; chroma interpolates linearly)
 template <typename PX, bool CHROMA> CTU_DEV void leaf_ang_row(lds<PX> *S, const lf_mode &M, int yd, int (&out)[4])
@@ -218,22 +247,27 @@ template <typename PX, bool CHROMA> CTU_DEV void leaf_ang_row(lds<PX> *S, const 
   }
 }
 
-// the prediction of sample e = lane & 15 of the 4x4 block for the (wave-uniform) mode
-template <typename PX> CTU_DEV int leaf_predict(lds<PX> *S, wctx *V, int mode, int color)
+// the prediction of sample e = lane & 15 of the 4x4 block for the (wave-uniform) mode from the lane's reference rows (a row of 16
+// lanes may have its own)
+template <typename PX> CTU_DEV int leaf_predict(lds<PX> *S, CTU_LDS const uint16_t *top, CTU_LDS const uint16_t *left, int mode, int color)
 {
   const int e = CTU_TID & 15, x = e & 3, y = e >> 2;
   int out[4];
   if (mode < 2) {
-    const ref_rows_t<CTU_LDS const uint16_t *> R = {LDSP(const uint16_t, V->top), LDSP(const uint16_t, V->left), LDSP(const uint16_t, V->top), LDSP(const uint16_t, V->left)};
+    const ref_rows_t<CTU_LDS const uint16_t *> R = {top, left, top, left};
     const mode_info M = make_mode_info(mode, 4, 4, color != 0);        // (planar / DC: no table behind it; never the smoothed rows for 4x4)
     const int dc = mode == 1 ? dc_value(R.top, R.left, 4, 4) : 0;
     predict_row<4>(M, R, dc, color != 0, 4, 4, y, 0, (int)px_info<PX>::maxv, out);
     return x == 0 ? out[0] : x == 1 ? out[1] : x == 2 ? out[2] : out[3];
   }
-  const lf_mode M = leaf_mode(S, V, mode);
+  const lf_mode M = leaf_mode(S, top, left, mode);
   const int xd = M.vertical ? x : y, yd = M.vertical ? y : x;
   if (color) leaf_ang_row<PX, true>(S, M, yd, out); else leaf_ang_row<PX, false>(S, M, yd, out);
   return xd == 0 ? out[0] : xd == 1 ? out[1] : xd == 2 ? out[2] : out[3];
+}
+template <typename PX> CTU_DEV int leaf_predict(lds<PX> *S, wctx *V, int mode, int color)
+{
+  return leaf_predict(S, LDSP(const uint16_t, V->top), LDSP(const uint16_t, V->left), mode, color);
 }
 
 // ---- most probable modes, mode bits ----------------------------------------------------------------------------------------------
@@ -813,10 +847,229 @@ template <typename PX> CTU_INLINE1 CTU_DEV lf_block leaf_recon_inl(lds<PX> *S, c
   LF_T(8);
   return B;
 }
-// (an out-of-line call saves and reloads ~45 callee-saved VGPRs through the stack -- 2.5 k cycles a block: the CU evaluations have ONE
-// call site each, a loop over the colours around the inlined body; the rare helper goes through this copy)
-template <typename PX> CTU_NOINLINE CTU_DEV lf_block leaf_recon(lds<PX> *S, const job<PX> &J, wctx *V, int color, int mode, int cbf_u, int x, int y, int lx, int ly, int n,
-                                                               int refs_ready, PX *dst_, int dp, int16_t *co, int cp)
+// (an out-of-line call saves and reloads ~45 callee-saved VGPRs through the stack -- 2.5 k cycles a block: eval_cu4 inlines this
+// body and the joint pass below, each at its ONE call site)
+
+// ---- several blocks in one pass: a block per ROW of 16 lanes -----------------------------------------------------------------------
+// A block pass keeps 16 lanes busy and the three other rows of the wave repeat them.  Where blocks do not depend on each other's
+// reconstruction -- the Cb and Cr blocks of an 8x8 area, and beside them the luma block of the 4x4 CU that carries them (no CCLM: the
+// chroma blocks read that CU's luma MODE only) -- every row works on a block of its own: one pass instead of two or three.
+// Row layout: 0 luma (LUMA) or Cb again, 1 Cb, 2 Cr priced with cbf_cb = 0, 3 Cr priced with cbf_cb = 1.  The only coupling between
+// the blocks is the context of Cr's coded block flag (M_CBF_CR + cbf_cb, the last section of uvg_rdoq): Cr is carried under both
+// hypotheses in the two rows nobody else needs -- no instruction more than one Cr block -- and the row that matches Cb's flag is kept.
+#define LF_DESC16(X) X(15) X(14) X(13) X(12) X(11) X(10) X(9) X(8) X(7) X(6) X(5) X(4) X(3) X(2) X(1) X(0)
+// lane L of the lane's own row of 16 (DPP row_newbcast: every lane of the row is a valid source, the whole wave must be active)
+template <int L> CTU_DEV int lf_rb(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x150 + L, 0xf, 0xf, true); }
+template <int L> CTU_DEV double lf_rb64(double v) { return __hiloint2double(lf_rb<L>(__double2hiint(v)), lf_rb<L>(__double2loint(v))); }
+// the ballot of the lane's own row
+CTU_DEV unsigned lf_row_ballot(bool p) { return (unsigned)(__ballot(p) >> (CTU_TID & 48)) & 0xffffu; }
+CTU_DEV int lf_rows_min(int v)
 {
-  return leaf_recon_inl(S, J, V, color, mode, cbf_u, x, y, lx, ly, n, refs_ready, dst_, dp, co, cp);
+  const int a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16), c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
+  const int ab = a < b ? a : b, cd = c < d ? c : d;
+  return ab < cd ? ab : cd;
+}
+
+// leaf_rdoq with a block per row: coef / color / cbf_u / lambda are the lane's row's.  Every sum a block forms is formed by its row in
+// the reference's scan order (the values of the row's owners arrive by DPP row broadcast); what is wave-uniform for one block -- no
+// candidate at all, the last candidate, the end of the last-position search -- is a predicate of the row, inside loops bounded by the
+// rows' extremes; the fixed point runs until no row changes (a row that is done is a fixed point of further rounds: the update is a
+// function of the current levels).  Returns the lane's level; *has_out = any level of the lane's row survived.
+template <typename PX> CTU_DEV int leaf_rdoq_rows(lds<PX> *S, int coef, int color, int cbf_u, double lambda, int *has_out)
+{
+  const int lane = CTU_TID, r = lane & 15, px = r & 3, py = r >> 2;
+  const uint32_t tab = LDSP(const uint32_t, S->lf_rq)[r];
+  const unsigned later = tab & 0xffffu;                     // raster positions later in scan order
+  const int sp = (int)((tab >> 16) & 15), next_r = (int)((tab >> 20) & 15);
+  rdoq_env E;
+  E.st = S->rdoq_state; E.t = color ? 1 : 0; E.lambda = lambda;
+  E.q_bits = LDSP(const int32_t, S->lf_qbits)[E.t];
+  E.q = LDSP(const int32_t, S->lf_q)[E.t];
+  E.error_scale = LDSP(const double, S->lf_escale)[E.t];
+  const int cap_half = 1 << (E.q_bits - 1);
+  const int32_t cap = 0x7fffffff - cap_half;
+  const int ac = iabs_(coef);
+  const int64_t prod = (int64_t)ac * E.q;
+  const int32_t level_double = (int32_t)(prod < cap ? prod : cap);
+  const int mal = (int)((uint32_t)(level_double + cap_half) >> E.q_bits);
+  const double c0 = (double)level_double * (double)level_double * E.error_scale;
+  if (__ballot(mal > 0) == 0) { *has_out = 0; return 0; }
+  const unsigned nz = lf_row_ballot(mal > 0);
+  const bool act = nz != 0;                                 // the row has a candidate
+  // the last candidate in scan order: the one with no candidate later than it (one lane of an active row)
+  const bool is_last = mal > 0 && (nz & later) == 0;
+  const int last_sp = lf_row_sum(is_last ? sp : 0);
+  const bool mine = act && sp <= last_sp;
+  const int min_last = lf_rows_min(act ? last_sp : 15), max_last = -lf_rows_min(-last_sp);
+  // the positions behind the last candidate only add their level-0 cost (rdo.c:1556-1583), in descending scan order
+  // (a row's predicate "behind / up to its last candidate" is applied by the OWNER of a value, which sends +0.0 otherwise: adding it
+  // changes nothing -- every sum here is >= +0 or compared only -- and the steps need no divergent branch; the two sums start equal)
+  double block_uncoded_cost = 0, base_cost;
+  {
+    const double c0_behind = sp > last_sp ? c0 : 0.0;
+#define LF_STEP(k) if ((k) >= 1 && (k) > min_last) block_uncoded_cost += lf_rb64<LF_SCAN(k)>(c0_behind);
+    LF_DESC16(LF_STEP)
+#undef LF_STEP
+    base_cost = block_uncoded_cost;
+  }
+  // the Rice parameter a regular-coded position inherits: from the INPUT coefficients around the position coded before it (rdo.c:1697)
+  int go_rice_reg = 0;
+  {
+    int16_t sum = 0;
+    const int a1 = lf_nb<1>(ac), a2 = lf_nb<2>(ac), a5 = lf_nb<5>(ac), a4 = lf_nb<4>(ac), a8 = lf_nb<8>(ac);
+    if (px < 3) { sum = (int16_t)(sum + a1); if (px < 2) sum = (int16_t)(sum + a2); if (py < 3) sum = (int16_t)(sum + a5); }
+    if (py < 3) { sum = (int16_t)(sum + a4); if (py < 2) sum = (int16_t)(sum + a8); }
+    int v = sum - 20;
+    v = v < 31 ? v : 31;
+    const int t_in = go_rice_par((unsigned)(v > 0 ? v : 0));
+    const int nb = lf_shfl(t_in, (lane & 48) + next_r);
+    if (mine && sp != 15 && !is_last) go_rice_reg = nb;
+  }
+  // ---- the groups' decisions: a fixed point over the DAG "later in scan order", all rows together ----
+  int lev = mine ? mal : 0;
+  double cc = 0, cs = 0;
+  for (;;) {
+    const int l1 = lf_nb<1>(lev), l2 = lf_nb<2>(lev), l5 = lf_nb<5>(lev), l4 = lf_nb<4>(lev), l8 = lf_nb<8>(lev);
+    const int spend = mine ? (lev < 2 ? lev : 3) + (is_last ? 0 : 1) : 0;
+    const unsigned m0 = lf_row_ballot(spend & 1) & later, m1 = lf_row_ballot(spend & 2) & later, m2 = lf_row_ballot(spend & 4) & later;
+    const int spent = __popc(m0) + 2 * __popc(m1) + 4 * __popc(m2);
+    const bool regular = 28 - spent >= 4;
+    int level = 0;
+    if (mine) {
+      int ctx_sig = 0, ctx_set = 0, tsum_lev = 0;
+      {
+        int num_pos = 0, sum_abs = 0;
+#define LF_UPD(v) { const int a = (v); sum_abs += (4 + (a & 1)) < a ? (4 + (a & 1)) : a; num_pos += a ? 1 : 0; tsum_lev += a; }
+        if (px < 3) { LF_UPD(l1); if (px < 2) LF_UPD(l2); if (py < 3) LF_UPD(l5); }
+        if (py < 3) { LF_UPD(l4); if (py < 2) LF_UPD(l8); }
+#undef LF_UPD
+        if (!is_last) {
+          const int diag = px + py;
+          ctx_sig = (((sum_abs + 1) >> 1) < 3 ? ((sum_abs + 1) >> 1) : 3) + (diag < 2 ? 4 : 0);
+          if (color == 0) ctx_sig += diag < 5 ? 4 : 0;
+          const int tsum = sum_abs - num_pos;
+          ctx_set = ((tsum < 4 ? tsum : 4) + 1) + (!diag ? ((color == 0) ? 15 : 5) : (color == 0) ? (diag < 3 ? 10 : (diag < 10 ? 5 : 0)) : 0);
+        }
+      }
+      int go_rice = go_rice_reg;
+      if (!regular) { const int v = tsum_lev < 31 ? tsum_lev : 31; go_rice = go_rice_par((unsigned)v); }      // template_abs_sum(dst, 0, ...)
+      cs = 0;
+      level = (int)coded_level(E, &cc, c0, &cs, level_double, (uint32_t)mal, ctx_sig, ctx_set, go_rice, regular ? 4u : 0u, is_last);
+    }
+    const bool changed = mine && level != lev;
+    lev = level;
+    if (__ballot(changed) == 0) break;
+  }
+  // ---- the sums in scan order (rdo.c:1689-1772; one group: no group decision) ----
+  {
+    const double c0_in = sp <= last_sp ? c0 : 0.0, cc_in = mine ? cc : 0.0;
+#define LF_STEP(k) if ((k) <= max_last) { block_uncoded_cost += lf_rb64<LF_SCAN(k)>(c0_in); base_cost += lf_rb64<LF_SCAN(k)>(cc_in); }
+    LF_DESC16(LF_STEP)
+#undef LF_STEP
+  }
+  // ---- coded block flag and the last significant position (rdo.c:1774-1833) ----
+  double best_cost;
+  int best_last_idx_p1 = 0;
+  {
+    const int o_cbf = color == 0 ? M_CBF_LUMA : color == 1 ? M_CBF_CB : M_CBF_CR + (cbf_u ? 1 : 0);
+    best_cost = block_uncoded_cost + lambda * rbits(E, o_cbf, 0);
+    base_cost += lambda * rbits(E, o_cbf, 1);
+  }
+  double klast = 0;
+  if (lev) {
+    const int32_t *last_x_bits = S->last_bits + last_bits_off(E.t, 2, 0), *last_y_bits = S->last_bits + last_bits_off(E.t, 2, 1);
+    const double cl = last_x_bits[px] + last_y_bits[py];
+    klast = lambda * cl;
+  }
+  // a step of the search: a position with a level is a candidate for the last one and, at level 1, leaves base_cost - cc + c0; one
+  // without leaves base_cost - cs (+ 0.0); the first level above 1 ends the row's search (what base_cost becomes after that, nobody reads)
+  const double sub = lev ? cc : cs, add = lev ? c0 : 0.0;          // (lev, cs: 0 beyond the row's last candidate)
+  bool open = act;                                          // the row's search for the last position still runs
+#define LF_STEP(k) if ((k) <= max_last) { \
+    const int level = lf_rb<LF_SCAN(k)>(lev); \
+    const double total = base_cost + lf_rb64<LF_SCAN(k)>(klast) - lf_rb64<LF_SCAN(k)>(cs); \
+    const bool better = open && level != 0 && total < best_cost; \
+    best_cost = better ? total : best_cost; \
+    best_last_idx_p1 = better ? (k) + 1 : best_last_idx_p1; \
+    base_cost -= lf_rb64<LF_SCAN(k)>(sub); \
+    base_cost += lf_rb64<LF_SCAN(k)>(add); \
+    open = open && level <= 1; }
+  LF_DESC16(LF_STEP)
+#undef LF_STEP
+  const bool has = act && best_last_idx_p1 > 0;
+  *has_out = has;
+  return has && sp < best_last_idx_p1 ? (coef < 0 ? -lev : lev) : 0;
+}
+
+// The blocks of the 8x8 area (cx, cy) / (clx, cly) -- Cb and Cr, and with LUMA the luma block of the 4x4 CU (x, y) / (lx, ly) that
+// carries them, whose reference rows are in V->top / V->left -- in ONE pass of leaf_recon_inl's steps.  (tu, lu) / (tv, lv): where the
+// two chroma blocks' reference rows go (LDS, 17 entries each; with LUMA, V->top / V->left may serve Cr: the luma prediction is taken
+// first).  Outputs as leaf_recon_inl's, per block.
+struct lf_blocks { int cbf, ssd_y, ssd_u, ssd_v, lev_y, lev_u, lev_v; };      // (the levels: of position lane & 15, in every row)
+template <typename PX, bool LUMA> CTU_INLINE1 CTU_DEV lf_blocks leaf_recon_rows(lds<PX> *S, const job<PX> &J, wctx *V, int mode, int x, int y, int lx, int ly,
+                                                                               int cx, int cy, int clx, int cly, uint16_t *tu, uint16_t *lu, uint16_t *tv, uint16_t *lv,
+                                                                               PX *ry, PX *ru, PX *rv, int dpy, int dpc, int16_t *ky, int16_t *ku, int16_t *kv, int cpy, int cpc)
+{
+  const int depth = (int)px_info<PX>::depth;
+  const int lane = CTU_TID, row = lane >> 4, e = lane & 15, r = e >> 2, q = e & 3;
+  const int color = row >= 2 ? 2 : (LUMA && row == 0 ? 0 : 1);
+  LF_T0();
+  int pred_y = 0;
+  if (LUMA) pred_y = leaf_predict(S, V, mode, 0);
+  leaf_refs<PX, true>(S, J.P, tu, lu, 1, cx, cy, clx, cly, 8, tv, lv);
+  LF_T(5);
+  int pred = leaf_predict(S, LDSP(const uint16_t, color == 2 ? tv : tu), LDSP(const uint16_t, color == 2 ? lv : lu), mode, 1);
+  if (LUMA) pred = color == 0 ? pred_y : pred;
+  const int src = leaf_src(S, color, lx, ly);
+  int v = (int)(int16_t)(src - pred);
+  v = lf_fwd_pass(v, 2 - 1 + depth - 8);
+  v = lf_fwd_pass(v, 2 + 6);
+  int has;
+  LF_T(6);
+  const int level = leaf_rdoq_rows(S, v, color, row == 3, color ? J.P.c_lambda_tu : J.P.lambda, &has);
+  LF_T(7);
+  // Cb's flag picks Cr's row
+  const int has_y = LUMA ? __builtin_amdgcn_readlane(has, 0) : 0, has_u = __builtin_amdgcn_readlane(has, 16);
+  const int vrow = 2 + has_u;
+  const int has_v = __builtin_amdgcn_readlane(has, vrow * 16);
+  const bool keep = row == vrow || row == 1 || (LUMA && row == 0);
+  CTU_LDS int16_t *const lvl = LDSP(int16_t, lv_of(V, color));
+  int16_t *const co = color == 0 ? ky : (color == 1 ? ku : kv);
+  const int cp = color == 0 ? cpy : cpc, dp = color == 0 ? dpy : dpc;
+  if (keep) { lvl[e] = (int16_t)level; co[r * cp + q] = (int16_t)level; }
+  int rec = pred;
+  if (__ballot(has != 0) != 0) {
+    const int transform_shift = 15 - depth - 2;
+    const int shift = 20 - 14 - transform_shift;
+    const int qy = scaled_qp<PX>(J.P, 0), qc = scaled_qp<PX>(J.P, 1);
+    const int32_t scale_y = (int32_t)kInvQuantScales[qy % 6] << (qy / 6), scale_c = (int32_t)kInvQuantScales[qc % 6] << (qc / 6);
+    const int32_t scale = color == 0 ? scale_y : scale_c;
+    const int32_t add = 1 << (shift - 1);
+    int t = clampi((level * scale + add) >> shift, -32768, 32767);          // uvg_dequant, quant-generic.c:618-669
+    t = lf_inv_pass(t, 7);
+    t = lf_inv_pass(t, 12 - (depth - 8));
+    const int16_t val = (int16_t)(t + pred);
+    rec = has ? clampi(val, 0, (int)px_info<PX>::maxv) : pred;
+  }
+  PX *const dst_ = color == 0 ? ry : (color == 1 ? ru : rv);
+  if (keep) LDSP(PX, dst_)[r * dp + q] = (PX)rec;
+  int dd = src - rec;
+  dd = lf_row_sum(dd * dd) >> (2 * (depth - 8));
+  lf_blocks B;
+  B.cbf = has_y | has_u << 1 | has_v << 2;
+  B.ssd_y = LUMA ? __builtin_amdgcn_readlane(dd, 0) : 0;
+  B.ssd_u = __builtin_amdgcn_readlane(dd, 16);
+  B.ssd_v = __builtin_amdgcn_readlane(dd, vrow * 16);
+  B.lev_y = LUMA ? lf_shfl(level, e) : 0;
+  B.lev_u = lf_shfl(level, 16 + e);
+  B.lev_v = lf_shfl(level, vrow * 16 + e);
+  CTU_SYNC();
+  LF_T(8);
+  return B;
+}
+// the Cb and Cr blocks of an 8x8 CU, out of line (the depth wave's evaluation: eval_cu)
+template <typename PX> CTU_NOINLINE CTU_DEV lf_blocks leaf_recon_uv(lds<PX> *S, const job<PX> &J, wctx *V, int mode, int x, int y, int lx, int ly, PX *ru, PX *rv, int dpc,
+                                                                   int16_t *ku, int16_t *kv, int cpc)
+{
+  return leaf_recon_rows<PX, false>(S, J, V, mode, x, y, lx, ly, x, y, lx, ly, V->top, V->left, V->ftop, V->fleft, nullptr, ru, rv, 0, dpc, nullptr, ku, kv, 0, cpc);
 }
