@@ -1997,7 +1997,25 @@ CTU_DEV int rec_spend(uint32_t rec) { const uint32_t a = rec & 0xffffu; return (
 // each lane owns ONE model and walks the positions in coding order, adapting its model at the bins that use it -- two sweeps
 // (sig / gt1 / parity, then gt2) cover the <= 75 models of a block.  Lane 0 codes the last-position prefix and the group flags.
 // All 64 lanes of wave 0 call it; the returned value is the same on every lane.  Host emulation: the serial walk.
-template <typename PX> CTU_NOINLINE CTU_DEV double coeff_bits(lds<PX> *S, uint32_t *m_, int update, const int16_t *coeff_, int n, int color)
+// BITS = false: the models' adaptation only (the coder's pass: nobody reads the count; returns 0).  No Rice parameters, no entropy-table
+// lookups, no bypass pass, no sums: the sweep's sixteen steps per group are unrolled on v_readlane at fixed lanes, each a compare and
+// a packed state update in registers (cb_step), and the last-position prefix and the group flags -- lane 0's chain of LDS
+// read-modify-writes in the counting variant -- are models in lanes' registers as well (the prefix's: a lane each, at most four
+// bins; the two group-flag contexts: two lanes, stepped through the groups from ballots).
+#if defined(__HIPCC__)
+typedef unsigned short cb_u16x2 __attribute__((ext_vector_type(2)));
+// CTX_UPDATE (m_update) on the packed state: both halves shifted by their own window (v_pk_lshrrev_b16); no borrow or carry crosses
+// the halves (a state never exceeds 0x7fe0 / 0x7ffe, what is taken off never the state).  gate: 0x7ffe7fe0 where the model codes
+// the bin, else 0; add: the windows' (0x7fff >> rate) & mask where that bin is 1, else 0
+CTU_DEV uint32_t cb_step(uint32_t st, uint32_t rpk, uint32_t gate, uint32_t add)
+{
+  const cb_u16x2 sh = __builtin_bit_cast(cb_u16x2, st) >> __builtin_bit_cast(cb_u16x2, rpk);
+  return st - (__builtin_bit_cast(uint32_t, sh) & gate) + add;
+}
+CTU_DEV uint32_t cb_rpk(int rw) { return (uint32_t)(rw >> 4) | (uint32_t)(rw & 15) << 16; }
+CTU_DEV uint32_t cb_addpk(int rw) { return ((0x7fffu >> (rw >> 4)) & 0x7fe0u) | ((0x7fffu >> (rw & 15)) & 0x7ffeu) << 16; }
+#endif
+template <typename PX, bool BITS = true> CTU_NOINLINE CTU_DEV double coeff_bits(lds<PX> *S, uint32_t *m_, int update, const int16_t *coeff_, int n, int color)
 {
   wctx *const V = wv_of(S);
 #if !defined(__HIPCC__)
@@ -2012,7 +2030,7 @@ template <typename PX> CTU_NOINLINE CTU_DEV double coeff_bits(lds<PX> *S, uint32
   const uint16_t *scan = scan_of(S, l2);
   CTU_LDS uint32_t *const m = (CTU_LDS uint32_t *)m_;
   typename mg_ptr<PX, const int16_t>::type const coeff = MGP(PX, const int16_t, coeff_);
-  if (n == 4) return coeff_bits4r(S, m, update, (int)coeff[lane & 15], color);          // (ctu_leaf4.h: the block from registers)
+  if (n == 4) return coeff_bits4r<PX, BITS>(S, m, update, (int)coeff[lane & 15], color);          // (ctu_leaf4.h: the block from registers)
   CTU_LDS uint32_t *recs = (CTU_LDS uint32_t *)(V->t0);       // t0 + t1: 1024 words, free while costs are counted
   CTU_LDS uint8_t *cgf = (CTU_LDS uint8_t *)V->cg_flag;                                   // per group (raster): has a level
   CTU_LDS int32_t *gtot = (CTU_LDS int32_t *)(V->rq_stage);   // per group (scan order): regular bins it would spend, bit 30: a level among k = 1..15
@@ -2042,7 +2060,8 @@ template <typename PX> CTU_NOINLINE CTU_DEV double coeff_bits(lds<PX> *S, uint32
     if (t && ctx_sig > 7) ctx_sig = 7;
     int ofs = 0;
     if (sp != last) ofs = ((tsum < 4 ? tsum : 4) + 1) + (!diag ? (color == 0 ? 15 : 5) : color == 0 ? (diag < 3 ? 10 : (diag < 10 ? 5 : 0)) : 0);
-    const int r4 = go_rice_par((unsigned)abs_sum_tmpl(coeff, px, py, n, 4)), r0 = go_rice_par((unsigned)abs_sum_tmpl(coeff, px, py, n, 0));
+    int r4 = 0, r0 = 0;
+    if constexpr (BITS) { r4 = go_rice_par((unsigned)abs_sum_tmpl(coeff, px, py, n, 4)); r0 = go_rice_par((unsigned)abs_sum_tmpl(coeff, px, py, n, 0)); }
     const int inferred = (sp & 15) == 0 && g != 0 && g != cg_last && !((gtot[g] >> 30) & 1);
     const int sig_coded = sp != last && !inferred;
     const int spend = sig_coded + (a ? 1 + (a > 1 ? 2 : 0) : 0);
@@ -2057,25 +2076,137 @@ template <typename PX> CTU_NOINLINE CTU_DEV double coeff_bits(lds<PX> *S, uint32
   }
   CTU_SYNC();
   // ---- where the regular-bin budget runs out (lane 0; whole groups while they fit) ----
-  if (lane == 0) {
-    int rb = (nn * 28) >> 4, sw = -1;
-    for (int g = cg_last; g >= 0 && sw < 0; --g) {
-      const int f = scan[g * 16];
-      const int sig_grp = cgf[((f >> l2) >> 2) * cgw + ((f & (n - 1)) >> 2)] || g == 0;
-      if (!sig_grp) continue;
-      const int tot = gtot[g] & 0xffff;
-      if (rb - tot >= 4) { rb -= tot; continue; }
-      for (int sp = (g == cg_last ? last : g * 16 + 15); sp >= g * 16; --sp) {
-        if (rb < 4) { sw = sp; break; }
-        rb -= rec_spend(recs[sp]);
-      }
-      if (sw < 0 && rb < 4) sw = g * 16 - 1;          // ran out exactly at the group's end: everything below is bypass-coded
-    }
-    V->rq_i[8] = sw;
+  bool walk = true;
+  if constexpr (!BITS) {
+    // every coded group passes whole while the coded groups' bins together leave 4 of the budget: then the walk below ends with -1
+    int mine = 0;
+    if (lane <= cg_last) { const int f = scan[lane * 16]; if (cgf[((f >> l2) >> 2) * cgw + ((f & (n - 1)) >> 2)] || lane == 0) mine = gtot[lane] & 0xffff; }
+    int all = 0;
+#pragma unroll
+    for (int b = 0; b < 7; ++b) all += __popcll(__ballot((mine >> b) & 1)) << b;          // (16 positions of at most 4 bins: 7 bits)
+    walk = ((nn * 28) >> 4) - all < 4;
   }
-  CTU_SYNC();
-  const int sw = V->rq_i[8];          // scan positions <= sw are bypass-coded
+  if (walk) {
+    if (lane == 0) {
+      int rb = (nn * 28) >> 4, sw = -1;
+      for (int g = cg_last; g >= 0 && sw < 0; --g) {
+        const int f = scan[g * 16];
+        const int sig_grp = cgf[((f >> l2) >> 2) * cgw + ((f & (n - 1)) >> 2)] || g == 0;
+        if (!sig_grp) continue;
+        const int tot = gtot[g] & 0xffff;
+        if (rb - tot >= 4) { rb -= tot; continue; }
+        for (int sp = (g == cg_last ? last : g * 16 + 15); sp >= g * 16; --sp) {
+          if (rb < 4) { sw = sp; break; }
+          rb -= rec_spend(recs[sp]);
+        }
+        if (sw < 0 && rb < 4) sw = g * 16 - 1;          // ran out exactly at the group's end: everything below is bypass-coded
+      }
+      V->rq_i[8] = sw;
+    }
+    CTU_SYNC();
+  }
+  const int sw = walk ? V->rq_i[8] : -1;          // scan positions <= sw are bypass-coded
   RQ_T(29);
+  if constexpr (!BITS) {
+    // ---- the models only ----
+    const int last_u = __builtin_amdgcn_readfirstlane(last), sw_u = __builtin_amdgcn_readfirstlane(sw), cgl = last_u >> 4, l15 = lane & 15;
+    CTU_LDS const uint8_t *const rate = LDSP(const uint8_t, kRate);
+    const uint32_t kGate = 0x7ffe7fe0u;
+    // per group (lane g, scan order; ncg <= 64): coded; its flag and the context of its flag (right or lower neighbour coded)
+    unsigned long long todo, flg_ctx, flg_bin;
+    {
+      int on = 0, ctx = 0, bin = 0;
+      if (lane <= cgl) {
+        const int f = scan[lane * 16], cx = (f & (n - 1)) >> 2, cy = (f >> l2) >> 2, cb = cy * cgw + cx;
+        bin = cgf[cb] != 0;
+        on = bin || lane == 0;
+        if (cx + 1 < cgw) ctx |= cgf[cb + 1] != 0;
+        if (cy + 1 < cgw) ctx |= cgf[cb + cgw] != 0;
+      }
+      const int gmin = (sw_u + 1) >> 4;                        // groups below it lie behind the budget's end
+      todo = __ballot(on) & (gmin < 64 ? ~0ull << gmin : 0ull);
+      flg_ctx = __ballot(ctx);
+      flg_bin = __ballot(bin);
+    }
+    // the sweep's models: sig / greater-1 / parity (/ greater-2: chroma) a lane each; luma: the lanes 0..20 own a greater-2 model too
+    int role = -1, k = 0;
+    if (t) { if (lane < 8) { role = 0; k = lane; } else if (lane < 41) { role = 1 + (lane - 8) / 11; k = (lane - 8) % 11; } }
+    else { if (lane < 12) { role = 0; k = lane; } else if (lane < 33) { role = 1; k = lane - 12; } else if (lane < 54) { role = 2; k = lane - 33; } }
+    const bool luma = __builtin_amdgcn_readfirstlane(t) == 0, two = luma && lane < 21;
+    const int model = role < 0 ? 0 : (role == 0 ? M_SIG + 12 * t : role == 1 ? M_GT1 + 21 * t : role == 2 ? M_PAR + 21 * t : M_GT2 + 21 * t) + k;
+    const int model2 = M_GT2 + 21 * t + (two ? lane : 0);
+    uint32_t st = m[model], st2 = m[model2];
+    const int rw = rate[model], rw2 = rate[model2];
+    const uint32_t rpk = cb_rpk(rw), addpk = cb_addpk(rw), rpk2 = cb_rpk(rw2), addpk2 = cb_addpk(rw2);
+    // a position's key per role, a byte each (sig, greater-1, parity, greater-2): context << 1 | bin, 0xff where it codes no such
+    // bin; a lane's model codes the bin where the byte of its role is 2 k or 2 k + 1
+    const uint32_t sh8 = role < 0 ? 0u : (uint32_t)role * 8u, k2 = role < 0 ? 0x1000u : (uint32_t)k << 1, l2k = two ? (uint32_t)lane << 1 : 0x1000u;
+    {
+      int g = 63 - __builtin_clzll(todo);                      // (the last position's group is coded and in front of the budget's end)
+      uint32_t nxt = recs[g * 16 + l15];
+      for (;;) {
+        const uint32_t rec = nxt;
+        const int spl = g * 16 + l15;
+        todo &= ~(1ull << g);
+        const bool more = todo != 0;
+        if (more) { g = 63 - __builtin_clzll(todo); nxt = recs[g * 16 + l15]; }          // (the next group's records: in flight during this group's steps)
+        const uint32_t a = rec & 0xffffu, cs = (rec >> 16) & 15u, of2 = ((rec >> 20) & 31u) << 1;
+        uint32_t keys = ((rec >> 29) & 1u ? cs << 1 | (a != 0 ? 1u : 0u) : 0xffu) | (a != 0 ? of2 | (a > 1 ? 1u : 0u) : 0xffu) << 8 |
+                        (a > 1 ? of2 | (a & 1u) : 0xffu) << 16 | (a > 1 ? of2 | (a >= 4 ? 1u : 0u) : 0xffu) << 24;
+        if (spl > last_u || spl <= sw_u) keys = 0xffffffffu;
+#pragma unroll
+        for (int j = 15; j >= 0; --j) {
+          const uint32_t kj = (uint32_t)__builtin_amdgcn_readlane((int)keys, j);
+          if (kj == 0xffffffffu) continue;                     // (wave-uniform)
+          const uint32_t d = ((kj >> sh8) & 0xffu) - k2;
+          st = cb_step(st, rpk, d < 2u ? kGate : 0u, d == 1u ? addpk : 0u);
+          if (luma && (kj >> 24) != 0xffu) {                   // (wave-uniform: the position codes a greater-2 bin)
+            const uint32_t d2 = (kj >> 24) - l2k;
+            st2 = cb_step(st2, rpk2, d2 < 2u ? kGate : 0u, d2 == 1u ? addpk2 : 0u);
+          }
+        }
+        if (!more) break;
+      }
+    }
+    if (role >= 0 && update) m[model] = st;
+    if (two && update) m[model2] = st2;
+    RQ_T(30);
+    // ---- last-position prefix (lanes 0..7: x, 8..15: y; model q of an axis sees the bins k >> sh == q: 1 below the position's
+    // group index, 0 at it unless it is the largest) and the group flags (lanes 16, 17: context 0, 1) ----
+    {
+      const int pos_last = scan[last_u];
+      const int last_y = pos_last >> l2, last_x = pos_last - (last_y << l2);
+      const int off = t ? 0 : (l2 == 3 ? 3 : (l2 == 4 ? 6 : 10));          // (prefix_ctx[l2] of the counting variant; n is 8, 16 or 32 here)
+      const int sh = t ? clampi(n >> 3, 0, 2) : ((l2 + 1) >> 2);
+      const int gmax = group_idx(n - 1), ax = (lane >> 3) & 1, q = lane & 7, gp = group_idx(ax ? last_y : last_x);
+      const int amodel = lane < 16 ? (ax ? M_LASTY : M_LASTX) + 20 * t + off + q : M_SIGGRP + 2 * t + (lane & 1);
+      uint32_t ast = m[amodel];
+      const int arw = rate[amodel];
+      const uint32_t arpk = cb_rpk(arw), aaddpk = cb_addpk(arw);
+      bool dirty = false;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int kk = (q << sh) + i;
+        const bool in = lane < 16 && i < (1 << sh), one = in && kk < gp, zero = in && kk == gp && gp < gmax;
+        ast = cb_step(ast, arpk, one || zero ? kGate : 0u, one ? aaddpk : 0u);
+        dirty |= one || zero;
+      }
+      unsigned long long rem = cgl >= 2 ? ((1ull << cgl) - 1) & ~1ull : 0ull;          // the groups cgl - 1 .. 1 code a flag
+      const int my = lane - 16;
+      while (rem) {
+        const int g = 63 - __builtin_clzll(rem);
+        rem &= ~(1ull << g);
+        const int c = (int)((flg_ctx >> g) & 1), b = (int)((flg_bin >> g) & 1);
+        const bool hit = my == c;
+        ast = cb_step(ast, arpk, hit ? kGate : 0u, hit && b ? aaddpk : 0u);
+        dirty |= hit;
+      }
+      if (dirty && update) m[amodel] = ast;          // (only a model that coded a bin: the others may be another wave's)
+    }
+    CTU_SYNC();
+    RQ_T(31);
+    return 0.0;
+  }
   // ---- the models, one per lane, along the positions in coding order ----
   // A group's 16 records are fetched by lanes 0..15 at once and handed out with v_readlane: no memory in the adaptation chain.
   // 4x4 luma blocks use 16 of the 21 greater-1 / parity / greater-2 models (the diagonal classes of larger blocks never occur) and
@@ -3231,18 +3362,18 @@ template <typename PX> CTU_NOINLINE CTU_DEV void coder_pass(lds<PX> *S, const jo
         const int l2 = ilog2_dev(tn);
         PAR_FOR(e, tn * tn) lv_of(V, 0)[e] = CTU_GLOAD(&co[(e >> l2) * LCU + (e & (tn - 1))]);
         CTU_SYNC();
-        (void)coeff_bits(S, m, 1, lv_of(V, 0), tn, 0);
+        (void)coeff_bits<PX, false>(S, m, 1, lv_of(V, 0), tn, 0);
       }
       if ((parts & CODER_CHROMA) && has_c) {
         if (au) {
           PAR_FOR(e, cw * cw) lvu[e] = CTU_GLOAD(&J.coeff[4096 + (cby + (e >> cl2)) * LCU_C + cbx + (e & (cw - 1))]);
           CTU_SYNC();
-          (void)coeff_bits(S, m, 1, lvu, cw, 1);
+          (void)coeff_bits<PX, false>(S, m, 1, lvu, cw, 1);
         }
         if (av) {
           PAR_FOR(e, cw * cw) lvv[e] = CTU_GLOAD(&J.coeff[5120 + (cby + (e >> cl2)) * LCU_C + cbx + (e & (cw - 1))]);
           CTU_SYNC();
-          (void)coeff_bits(S, m, 1, lvv, cw, 2);
+          (void)coeff_bits<PX, false>(S, m, 1, lvv, cw, 2);
         }
       }
       CTU_SYNC();

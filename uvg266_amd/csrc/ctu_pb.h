@@ -2058,10 +2058,10 @@ template <typename PX> CTU_NOINLINE CTU_DEV void coder_pass_pb(lds<PX> *S, const
           if (!is_inter || n == 64 || cb_u || cb_v) m_code(m, 1, M_CBF_LUMA + 0, cb_y, dummy);
         }
         CTU_SYNC();
-        if (cb_y) (void)coeff_bits(S, m, 1, lv_of(V, 0), tn, 0);
+        if (cb_y) (void)coeff_bits<PX, false>(S, m, 1, lv_of(V, 0), tn, 0);
         if (!sep) {
-          if (cb_u) (void)coeff_bits(S, m, 1, lv_of(V, 1), tn >> 1, 1);
-          if (cb_v) (void)coeff_bits(S, m, 1, lv_of(V, 2), tn >> 1, 2);
+          if (cb_u) (void)coeff_bits<PX, false>(S, m, 1, lv_of(V, 1), tn >> 1, 1);
+          if (cb_v) (void)coeff_bits<PX, false>(S, m, 1, lv_of(V, 2), tn >> 1, 2);
         } else if (last4) {
           const cu4 *a = cu_at(S, lx & ~7, ly & ~7);
           const int au = (a->cbf >> 1) & 1, av = (a->cbf >> 2) & 1;
@@ -2071,8 +2071,8 @@ template <typename PX> CTU_NOINLINE CTU_DEV void coder_pass_pb(lds<PX> *S, const
             m_code(m, 1, M_CBF_CR + au, av, dummy);
           }
           CTU_SYNC();
-          if (au) (void)coeff_bits(S, m, 1, lv_of(V, 1), 4, 1);
-          if (av) (void)coeff_bits(S, m, 1, lv_of(V, 2), 4, 2);
+          if (au) (void)coeff_bits<PX, false>(S, m, 1, lv_of(V, 1), 4, 1);
+          if (av) (void)coeff_bits<PX, false>(S, m, 1, lv_of(V, 2), 4, 2);
         }
       }
       CTU_SYNC();
