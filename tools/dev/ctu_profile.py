@@ -34,3 +34,6 @@ lfn = ["area source load", "refs (luma)", "src->sgpr, mpm, planar/DC", "pass A (
 print("4x4 leaf, cycles per CTU (walk's wave):")
 for i, nm in enumerate(lfn):
     if nm != "-": print("  %-44s %10.0f   per CU %7.0f" % (nm, lf[:, i].mean(), lf[:, i].mean() / 256))
+print("the walk waits for a depth wave's cost of the unsplit CU (wait_eval), cycles per CTU (walk's wave):")
+for i, nm, per in ((10, "depth 1 (32x32)", 4), (14, "depth 2 (16x16)", 16), (15, "depth 3 (8x8)", 64)):
+    print("  %-44s %10.0f   per area %7.0f" % (nm, lf[:, i].mean(), lf[:, i].mean() / per))

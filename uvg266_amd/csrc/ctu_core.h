@@ -115,6 +115,7 @@
 //   RQ_T0(W) ... RQ_T(slot)    consecutive phases of one function, each ending at its mark, into scratch::prof[wave][slot]
 //   LF_T0() ... LF_T(slot)     the same for the 4x4 leaf on the walk's wave, into scratch::prof_lf[slot] (`J` in scope); LF_TR():
 //                              restart the interval after a step that counted itself
+//   WAIT_EVAL(S, L)            wait_eval, and how long the walk stood in it, into scratch::prof_lf[10 / 14 / 15] for depth 1 / 2 / 3
 //   PB_COUNT, CTU_PROF_RESET / PB_PROF_RESET: the counters and the reset that are not a phase
 // RQ_T0 and the last group stand as statements WITHOUT a semicolon of their own: a build without the switch has no token there.
 #if defined(__HIPCC__) && defined(CTU_PROFILE)
@@ -125,6 +126,7 @@
 #define LF_T0() unsigned long long tq = __builtin_amdgcn_s_memtime()
 #define LF_T(slot) do { const unsigned long long t2 = __builtin_amdgcn_s_memtime(); if (CTU_TID == 0 && CTU_WAVE == 0) J.W->prof_lf[slot] += t2 - tq; tq = t2; } while (0)
 #define LF_TR() do { tq = __builtin_amdgcn_s_memtime(); } while (0)          // restart: what ran since the last mark counted itself
+#define WAIT_EVAL(S, L) do { LF_T0(); wait_eval(S, L); LF_T((L) <= 1 ? 10 : 12 + (L)); } while (0)
 #define CTU_PROF_RESET(S, J) BLK_FOR(i, 4 * 32) (J).W->prof[i >> 5][i & 31] = 0; BLK_FOR(i, 16) (J).W->prof_lf[i] = 0; (S)->prof_w = (J).W;
 #define PB_T0() const unsigned long long pb_t0__ = __builtin_amdgcn_s_memtime()
 #if defined(CTU_PROFILE_WALK)      // only the walk's wave counts the phases of eval_pb (slots < 14): they add up to its time
@@ -142,6 +144,7 @@
 #define LF_T0() ((void)0)
 #define LF_T(slot) ((void)0)
 #define LF_TR() ((void)0)
+#define WAIT_EVAL(S, L) wait_eval(S, L)
 #define CTU_PROF_RESET(S, J)
 #define PB_T0() ((void)0)
 #define PB_T1(W, slot) ((void)0)
@@ -1346,7 +1349,8 @@ template <typename DP> CTU_NOINLINE CTU_DEV rdoq_pos rdoq_decide(const rdoq_env 
 //     This needs the regular-bin budget not to run out inside the group (an upper bound from the candidates says so) or to have run
 //     out for good; the one or two groups where it does run out are walked position by position by lane 0;
 //   * the double-precision sums the reference forms in scan order (base cost, group statistics, the last-position search): every
-//     lane forms them, in the reference's order, from the owners' registers (v_readlane) -- no memory in the chain.
+//     lane forms them, in the reference's order, from the owners' registers (v_readlane at fixed lanes, sixteen unrolled steps per
+//     group; predicates applied by the owners, integers from ballots) -- no memory and no branch in the chain.
 // Result: V->rq_i[1] = whether any level survived; levels in dst.
 CTU_DEV double rl64(double v, int lane)
 {
@@ -1399,15 +1403,31 @@ template <typename PX> CTU_INLINE1 CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W
   const int lane = CTU_TID, sp = lane & 15;
   const bool own = lane < 16;
   // the positions behind the last candidate only add their level-0 cost (rdo.c:1556-1583), in descending scan order
-  double block_uncoded_cost = 0, base_cost = 0;
-  for (int top = nn - 16; top + 15 > last_scanpos; top -= 16) {
-    const int scanpos = top + sp;
-    const int64_t prod = (int64_t)iabs_((int)coef[scan[scanpos]]) * E.q;
-    const double err = (double)(int32_t)(prod < cap ? prod : cap);
-    const double c0 = err * err * E.error_scale;
-#pragma nounroll
-    for (int k = 15; k >= 0; --k) if (top + k > last_scanpos) { const double c = rl64(c0, k); block_uncoded_cost += c; base_cost += c; }
+  // The sums of this function run as sixteen unrolled steps per group on v_readlane at fixed lanes, without a branch in a step: the
+  // owner applies a step's predicate and hands +0.0 where the reference's walk skips.  Adding +0.0 is exact: every sum starts at
+  // +0.0 and x + y is -0.0 only for two negative zeros, so no sum here is ever -0.0 (and a zero's sign decides no comparison).
+  // block_uncoded_cost and base_cost receive the same values in the same order here: one sum, copied.
+  double tail_cost = 0;
+  {
+    const auto tail_c0 = [&](int top) -> double {
+      const int scanpos = top + sp;
+      const int64_t prod = (int64_t)iabs_((int)coef[scan[scanpos]]) * E.q;
+      const double err = (double)(int32_t)(prod < cap ? prod : cap);
+      return scanpos > last_scanpos ? err * err * E.error_scale : 0.0;
+    };
+    double nxt = nn - 1 > last_scanpos ? tail_c0(nn - 16) : 0.0;
+    for (int top = nn - 16; top + 15 > last_scanpos; top -= 16) {
+      const double c0 = nxt;
+      if (top - 1 > last_scanpos) nxt = tail_c0(top - 16);          // (the next group's loads: in flight during this group's steps)
+#pragma unroll
+      for (int k = 15; k >= 8; --k) tail_cost += rl64(c0, k);
+      if (top + 7 > last_scanpos) {                                // (wave-uniform: the lower half of the last candidate's group)
+#pragma unroll
+        for (int k = 7; k >= 0; --k) tail_cost += rl64(c0, k);
+      }
+    }
   }
+  double block_uncoded_cost = tail_cost, base_cost = tail_cost;
   if (CTU_TID == 0) for (int g = 0; g <= cg_last; ++g) cost_cg_sig[g] = 0;
   int reg_bins = (int)((uint32_t)(nn * 28) >> 4);
   CTU_SYNC();
@@ -1488,28 +1508,40 @@ template <typename PX> CTU_INLINE1 CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W
     }
     RQ_T(14);
     // the sums in scan order and the group's decision (rdo.c:1689-1772): every lane, from the owners' registers
-    double rd_coded = 0, rd_uncoded = 0, rd_sig = 0, rd_sig0 = 0;
-    int nnz_before_pos0 = 0, flag = 0, spent = 0;
-#pragma nounroll
-    for (int k = 15; k >= 0; --k) {
-      if (cgs * 16 + k > last_scanpos) continue;
-      const double kc = rl64(cc, k), ks = rl64(cs, k), k0 = rl64(c0, k);
-      const int level = __builtin_amdgcn_readlane(lev, k);
-      block_uncoded_cost += k0;
-      base_cost += kc;
-      // (the first position of a group other than group 0 resets the Rice parameter INSTEAD of paying: rdo.c:1690-1697)
-      if (!(k == 0 && cgs > 0)) spent += (level < 2 ? level : 3) + (cgs * 16 + k != last_scanpos);
-      if (cgs) {                                // the group statistics only matter where a group can be zeroed out
-        rd_sig += ks;
-        if (k == 0) rd_sig0 = ks;
-        if (level) {
-          flag = 1;
-          rd_coded += kc - ks;
-          rd_uncoded += k0;
-          if (k != 0) nnz_before_pos0++;
+    // (cc, cs, c0 and lev are zero beyond the last candidate and in lanes 16..63.)  What does not depend on the order comes from
+    // ballots: the bins spent, whether and where the group has levels.
+    double rd_coded = 0, rd_uncoded = 0, rd_sig = 0;
+    const unsigned m_nz = (unsigned)__ballot(lev != 0), m_gt1 = (unsigned)__ballot(lev > 1), m_mine = (unsigned)__ballot(mine);
+    // (the first position of a group other than group 0 resets the Rice parameter INSTEAD of paying: rdo.c:1690-1697; a position
+    // pays min(level, 2 -> 3) bins and one more unless it is the last)
+    const unsigned paying = cgs ? ~1u : ~0u, not_last = cgs == cg_last ? ~(1u << (last_scanpos & 15)) : ~0u;
+    const int spent = __popc(m_nz & paying) + 2 * __popc(m_gt1 & paying) + __popc(m_mine & paying & not_last);
+    const int nnz_before_pos0 = __popc(m_nz & ~1u);
+    int flag = cgs && m_nz;
+    const bool upper = cgs < cg_last || (last_scanpos & 15) >= 8;          // (wave-uniform: the last group may end in its lower half)
+    if (cgs) {                                  // the group statistics only matter where a group can be zeroed out
+      const double dc = lev ? cc - cs : 0.0, du = lev ? c0 : 0.0;
+      if (upper) {
+#pragma unroll
+        for (int k = 15; k >= 8; --k) {
+          block_uncoded_cost += rl64(c0, k); base_cost += rl64(cc, k);
+          rd_sig += rl64(cs, k); rd_coded += rl64(dc, k); rd_uncoded += rl64(du, k);
         }
       }
+#pragma unroll
+      for (int k = 7; k >= 0; --k) {
+        block_uncoded_cost += rl64(c0, k); base_cost += rl64(cc, k);
+        rd_sig += rl64(cs, k); rd_coded += rl64(dc, k); rd_uncoded += rl64(du, k);
+      }
+    } else {
+      if (upper) {
+#pragma unroll
+        for (int k = 15; k >= 8; --k) { block_uncoded_cost += rl64(c0, k); base_cost += rl64(cc, k); }
+      }
+#pragma unroll
+      for (int k = 7; k >= 0; --k) { block_uncoded_cost += rl64(c0, k); base_cost += rl64(cc, k); }
     }
+    const double rd_sig0 = rl64(cs, 0);
     if (fast && regular) reg_bins -= spent;
     int zeroed = 0;
     if (cgs) {
@@ -1593,21 +1625,35 @@ template <typename PX> CTU_INLINE1 CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W
         klast = lambda * cl;
       }
     }
-#pragma nounroll
-    for (int k = 15; k >= 0; --k) {
-      if (found_last || cgs * 16 + k > last_scanpos) continue;
-      const int level = __builtin_amdgcn_readlane(lev, k);
-      const double s_ = rl64(kcs, k);
-      if (level) {
-        const double total = base_cost + rl64(klast, k) - s_;
-        if (total < best_cost) { best_last_idx_p1 = cgs * 16 + k + 1; best_cost = total; }
-        if (level > 1) { found_last = 1; continue; }
-        base_cost -= rl64(kcc, k);
-        base_cost += rl64(k0, k);
-      } else {
-        base_cost -= s_;
+    // A position with a level is a candidate for the last one: base_cost + its position's bits - its significance flag, the first
+    // of equal totals in descending order wins; then its level's cost leaves base_cost and its level-0 cost comes back, while a
+    // zero's significance flag leaves it (and +0.0 comes back: k0 is zero there).  The walk ends at the first level above 1: known
+    // from a ballot, the positions below it are no candidates and base_cost is not read again.
+    const double kx = lev ? kcc : kcs;
+    const unsigned m_nz = (unsigned)__ballot(lev != 0), m_gt1 = (unsigned)__ballot(lev > 1);
+    const int kstop = m_gt1 ? 31 - __clz(m_gt1) : 0;
+    const unsigned cand = m_nz >> kstop << kstop;
+    if (cgs < cg_last || (last_scanpos & 15) >= 8) {              // (wave-uniform, as is kstop < 8 below)
+#pragma unroll
+      for (int k = 15; k >= 8; --k) {
+        const double total = base_cost + rl64(klast, k) - rl64(kcs, k);
+        const bool better = (cand >> k & 1u) != 0 && total < best_cost;
+        best_last_idx_p1 = better ? cgs * 16 + k + 1 : best_last_idx_p1;
+        best_cost = better ? total : best_cost;
+        base_cost = base_cost - rl64(kx, k) + rl64(k0, k);
       }
     }
+    if (kstop < 8) {
+#pragma unroll
+      for (int k = 7; k >= 0; --k) {
+        const double total = base_cost + rl64(klast, k) - rl64(kcs, k);
+        const bool better = (cand >> k & 1u) != 0 && total < best_cost;
+        best_last_idx_p1 = better ? cgs * 16 + k + 1 : best_last_idx_p1;
+        best_cost = better ? total : best_cost;
+        base_cost = base_cost - rl64(kx, k) + rl64(k0, k);
+      }
+    }
+    found_last = m_gt1 != 0;
   }
   if (CTU_TID == 0) V->rq_i[1] = best_last_idx_p1 > 0;
   RQ_T(17);
@@ -3169,7 +3215,7 @@ template <typename PX> CTU_DEV void search_ctu(lds<PX> *S, const job<PX> &J)
     }
     // a child of N came back with `ret`
     const bool known = !N.pending || eval_ready(S, L);      // is the CU's own cost there yet?  (only to stop early; never changes the outcome)
-    if (known && N.pending) wait_eval(S, L);
+    if (known && N.pending) WAIT_EVAL(S, L);
     SERIAL {
       N.split_cost += ret;
       const int k = N.child;
@@ -3192,7 +3238,7 @@ template <typename PX> CTU_DEV void search_ctu(lds<PX> *S, const job<PX> &J)
 #endif
     if (!V_flag(S)) { ++L; entering = 1; continue; }
     // the split is complete (or was cut short): the CU's own cost is needed now
-    if (N.pending) wait_eval(S, L);
+    if (N.pending) WAIT_EVAL(S, L);
     // The comparison is taken by every lane BEFORE lane 0 may overwrite a cost.
     const double factor = P.qp > 30 ? 1.1 : 1.075;
     const bool pruned = N.type != CU_NOTSET && N.split_bits * P.lambda + N.cost / factor > N.cost;      // the reference would not have tried the split (search.c:1952-1956)
