@@ -18,7 +18,11 @@ n_slots = min(2048, al(ctus, 32))          # a slot keeps the profile of the las
 ws = cs.ws.cpu().numpy()
 SZ = 68160
 prof = np.stack([ws[off_scr + i * SZ + SZ - 1024: off_scr + i * SZ + SZ].view(np.uint64).reshape(4, 32) for i in range(n_slots)]).astype(np.float64)
-lf = np.stack([ws[off_scr + i * SZ + SZ - 1024 - 128: off_scr + i * SZ + SZ - 1024].view(np.uint64) for i in range(n_slots)]).astype(np.float64)
+lf = np.stack([ws[off_scr + i * SZ + SZ - 1024 - 128: off_scr + i * SZ + SZ - 1024].view(np.uint64) for i in range(n_slots)])
+runs66 = (lf[:, 10] >> np.uint64(40)).astype(np.float64)          # slot 10 (LF_TN): cycles in the low 40 bits, the number of runs above them
+lf[:, 10] &= np.uint64((1 << 40) - 1)
+lf = lf.astype(np.float64)
+runs66 = runs66[prof[:, 0, 11] > 0]
 lf = lf[prof[:, 0, 11] > 0]
 prof = prof[prof[:, 0, 11] > 0]
 names = ["rough search", "refs+predict", "residual+transforms+recon", "RDOQ", "SSD", "RD cost bits", "unpark/models", "64x64 candidate", "coder pass", "load", "store", "TOTAL",
@@ -30,10 +34,11 @@ for i, nm in enumerate(names):
     print("  %-26s" % nm + "".join("%12.0f" % prof[:, w, i].mean() for w in range(4)))
 
 
-lfn = ["area source load", "refs (luma)", "src->sgpr, mpm, planar/DC", "pass A (modes 4..65)", "selection (+ pass B)", "recon: refs (chroma; joint pass: + the luma prediction)", "recon: predict + residual + DCT", "recon: RDOQ", "recon: dequant + IDCT + store + SSD", "fill_cu + between the named steps", "-", "bits: flags + mode bits (lane 0)", "bits: tr_cost (cbf + coeff_bits4)", "bits: cost + deblock marks"]
+lfn = ["area source load", "refs (luma)", "src->sgpr, mpm, planar/DC", "pass A (modes 2..65)", "selection", "recon: refs (chroma; joint pass: + the luma prediction)", "recon: predict + residual + DCT", "recon: RDOQ", "recon: dequant + IDCT + store + SSD", "fill_cu + between the named steps", "extra pass (mode 66), where a survivor lists it", "bits: flags + mode bits (lane 0)", "bits: tr_cost (cbf + coeff_bits4)", "bits: cost + deblock marks"]
 print("4x4 leaf, cycles per CTU (walk's wave):")
 for i, nm in enumerate(lfn):
-    if nm != "-": print("  %-44s %10.0f   per CU %7.0f" % (nm, lf[:, i].mean(), lf[:, i].mean() / 256))
+    print("  %-44s %10.0f   per CU %7.0f" % (nm, lf[:, i].mean(), lf[:, i].mean() / 256))
+print("  the extra pass runs for %.1f of a CTU's 256 4x4 CUs, %.0f cycles a run" % (runs66.mean(), lf[:, 10].sum() / max(runs66.sum(), 1)))
 print("the walk waits for a depth wave's cost of the unsplit CU (wait_eval), cycles per CTU (walk's wave):")
-for i, nm, per in ((10, "depth 1 (32x32)", 4), (14, "depth 2 (16x16)", 16), (15, "depth 3 (8x8)", 64)):
+for i, nm, per in ((14, "depths 1 and 2 (32x32, 16x16)", 20), (15, "depth 3 (8x8)", 64)):
     print("  %-44s %10.0f   per area %7.0f" % (nm, lf[:, i].mean(), lf[:, i].mean() / per))

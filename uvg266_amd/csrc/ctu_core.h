@@ -51,7 +51,8 @@
 //   switch        what it changes
 //   __HIPCC__     64 lanes and wave fences instead of one lane (the macros below); the 4x4 leaf on ctu_leaf4.h (lds::lf_*, eval_cu4,
 //                 coder_area4, a 4x4 arena share without the rough search's and RDOQ's arrays) -- the host keeps eval_cu for it;
-//                 its own rdoq_wave (the host's: ctu_rdoq_emul.h) and rough_costs; the depth waves' mailboxes instead of calls in
+//                 its own rdoq_wave (the host's: ctu_rdoq_emul.h), rough_costs and search_intra_rough (the selection in the lanes'
+//                 registers, rs_round; the host's goes through wctx::rs_*); the depth waves' mailboxes instead of calls in
 //                 place; the slim images: lds_cfg<uint16_t>::slim of the intra kernel (cand_px, the 32x32 arena share and the two
 //                 large scans in the workgroup's global scratch), lds_cfg<PX>::slim_scan with CTU_PB (the scans only)
 //   CTU_PB        NMX = 257 + 18 models per set; level_state::mot / fl / cbf4; wctx::rq_root; lds::pb .. cur64 (the inter state, the
@@ -114,8 +115,9 @@
 //   CTU_T0 / CTU_T1(W, slot)   a bracketed phase into scratch::prof[wave][slot]; PB_T0 / PB_T1: into scratch::prof_pb[slot]
 //   RQ_T0(W) ... RQ_T(slot)    consecutive phases of one function, each ending at its mark, into scratch::prof[wave][slot]
 //   LF_T0() ... LF_T(slot)     the same for the 4x4 leaf on the walk's wave, into scratch::prof_lf[slot] (`J` in scope); LF_TR():
-//                              restart the interval after a step that counted itself
-//   WAIT_EVAL(S, L)            wait_eval, and how long the walk stood in it, into scratch::prof_lf[10 / 14 / 15] for depth 1 / 2 / 3
+//                              restart the interval after a step that counted itself; LF_TN(slot): a step that does not run for
+//                              every CU -- its cycles in the low 40 bits, how often it ran above them
+//   WAIT_EVAL(S, L)            wait_eval, and how long the walk stood in it, into scratch::prof_lf[14 / 15] for depths 1 + 2 / 3
 //   PB_COUNT, CTU_PROF_RESET / PB_PROF_RESET: the counters and the reset that are not a phase
 // RQ_T0 and the last group stand as statements WITHOUT a semicolon of their own: a build without the switch has no token there.
 #if defined(__HIPCC__) && defined(CTU_PROFILE)
@@ -126,7 +128,8 @@
 #define LF_T0() unsigned long long tq = __builtin_amdgcn_s_memtime()
 #define LF_T(slot) do { const unsigned long long t2 = __builtin_amdgcn_s_memtime(); if (CTU_TID == 0 && CTU_WAVE == 0) J.W->prof_lf[slot] += t2 - tq; tq = t2; } while (0)
 #define LF_TR() do { tq = __builtin_amdgcn_s_memtime(); } while (0)          // restart: what ran since the last mark counted itself
-#define WAIT_EVAL(S, L) do { LF_T0(); wait_eval(S, L); LF_T((L) <= 1 ? 10 : 12 + (L)); } while (0)
+#define LF_TN(slot) do { const unsigned long long t2 = __builtin_amdgcn_s_memtime(); if (CTU_TID == 0 && CTU_WAVE == 0) J.W->prof_lf[slot] += (1ull << 40) + (t2 - tq); tq = t2; } while (0)
+#define WAIT_EVAL(S, L) do { LF_T0(); wait_eval(S, L); LF_T((L) <= 2 ? 14 : 15); } while (0)
 #define CTU_PROF_RESET(S, J) BLK_FOR(i, 4 * 32) (J).W->prof[i >> 5][i & 31] = 0; BLK_FOR(i, 16) (J).W->prof_lf[i] = 0; (S)->prof_w = (J).W;
 #define PB_T0() const unsigned long long pb_t0__ = __builtin_amdgcn_s_memtime()
 #if defined(CTU_PROFILE_WALK)      // only the walk's wave counts the phases of eval_pb (slots < 14): they add up to its time
@@ -144,6 +147,7 @@
 #define LF_T0() ((void)0)
 #define LF_T(slot) ((void)0)
 #define LF_TR() ((void)0)
+#define LF_TN(slot) ((void)0)
 #define WAIT_EVAL(S, L) wait_eval(S, L)
 #define CTU_PROF_RESET(S, J)
 #define PB_T0() ((void)0)
@@ -787,6 +791,97 @@ template <typename PX> CTU_NOINLINE CTU_DEV void rough_costs(lds<PX> *S, const j
 #endif
 }
 
+#if defined(__HIPCC__)
+// ---- the rough search's selection on one wave, the candidates where their costs are: in the lanes' registers ----
+// The reference keeps a three-entry list under strict "<" insertion (search_intra.c:1071-1215): the three smallest of everything
+// listed so far under (cost, insertion sequence).  A cost is >= +0, so its bit pattern orders like its value: the key.
+CTU_DEV uint64_t rs_key(double c) { return (uint64_t)(uint32_t)__double2hiint(c) << 32 | (uint32_t)__double2loint(c); }
+// the smallest value of the wave's lanes (wave-uniform): six DPP steps, the last two across the rows of 16.  All 64 lanes must be
+// active: a lane that is not reads as 0 in the first four steps.
+CTU_DEV uint32_t rs_wave_min(uint32_t v)
+{
+#define RS_MIN(x) { const uint32_t o = (uint32_t)(x); v = o < v ? o : v; }
+  RS_MIN(__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true));           // quad_perm [1,0,3,2]
+  RS_MIN(__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true));           // quad_perm [2,3,0,1]
+  RS_MIN(__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, true));          // row_half_mirror
+  RS_MIN(__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xf, 0xf, true));          // row_mirror
+  RS_MIN(__builtin_amdgcn_update_dpp((int)v, (int)v, 0x142, 0xa, 0xf, false));    // row_bcast:15 into rows 1 and 3
+  RS_MIN(__builtin_amdgcn_update_dpp((int)v, (int)v, 0x143, 0xc, 0xf, false));    // row_bcast:31 into rows 2 and 3
+#undef RS_MIN
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+// a candidate that is not in a lane: wave-uniform
+struct rs_extra { bool on; uint64_t key; int seq, mode; };
+struct rs_pick { int who; uint64_t key; };              // who: the lane, 64: the extra; key ~0: there was no candidate
+CTU_DEV bool rs_key_lt(uint32_t khi, uint32_t klo, uint64_t k) { return ((uint64_t)khi << 32 | klo) < k; }
+// the smallest candidate under (key, seq) among the lanes (on; key = khi : klo; seq >= 0, no two candidates with the same) and,
+// X, the extra: the minimum of the high words, among those that have it of the low words, among those of the sequence.  Most
+// picks end early: a lone candidate needs no reduction, and a high word that only one candidate has decides (costs that differ
+// at all nearly always differ there; the full ladder is for the ties of flat content).
+template <bool X> CTU_DEV rs_pick rs_pick_min(bool on, uint32_t khi, uint32_t klo, int seq, const rs_extra &x)
+{
+  const uint32_t none = 0xffffffffu;
+  const uint32_t xh = (uint32_t)(x.key >> 32), xl = (uint32_t)x.key;
+  const bool xon = X && x.on;
+  rs_pick r;
+  const unsigned long long b_on = __ballot(on);
+  const int n_on = __popcll(b_on) + (xon ? 1 : 0);
+  if (n_on == 0) { r.who = 0; r.key = ~0ull; return r; }
+  uint32_t mh = 0;
+  unsigned long long b1 = b_on;
+  bool y = xon;
+  if (n_on > 1) {
+    mh = rs_wave_min(on ? khi : none);
+    if (xon && xh < mh) mh = xh;
+    b1 = __ballot(on && khi == mh);
+    y = xon && xh == mh;
+  }
+  if (__popcll(b1) + (y ? 1 : 0) == 1) {
+    if (y) { r.who = 64; r.key = x.key; }
+    else {
+      r.who = __builtin_ctzll(b1);
+      r.key = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)khi, r.who) << 32 | (uint32_t)__builtin_amdgcn_readlane((int)klo, r.who);
+    }
+    return r;
+  }
+  const bool t1 = on && khi == mh;
+  uint32_t ml = rs_wave_min(t1 ? klo : none);
+  if (y && xl < ml) ml = xl;
+  const bool t2 = t1 && klo == ml, z = y && xl == ml;
+  uint32_t ms = rs_wave_min(t2 ? (uint32_t)seq : none);
+  r.key = (uint64_t)mh << 32 | ml;
+  if (z && (uint32_t)x.seq < ms) r.who = 64;
+  else {
+    const unsigned long long w = __ballot(t2 && (uint32_t)seq == ms);
+    r.who = w ? __builtin_ctzll(w) : 0;
+  }
+  return r;
+}
+// the survivors in rank order; a newcomer goes behind every entry that is not larger (strict "<", search_intra.c:1133-1142)
+struct rs_top3 { int m[3]; uint64_t k[3]; };
+CTU_DEV void rs_insert(rs_top3 &B, int mode, uint64_t key)
+{
+  if (key < B.k[0]) { B.k[2] = B.k[1]; B.m[2] = B.m[1]; B.k[1] = B.k[0]; B.m[1] = B.m[0]; B.k[0] = key; B.m[0] = mode; }
+  else if (key < B.k[1]) { B.k[2] = B.k[1]; B.m[2] = B.m[1]; B.k[1] = key; B.m[1] = mode; }
+  else if (key < B.k[2]) { B.k[2] = key; B.m[2] = mode; }
+}
+// one round's newcomers (a lane's: on, its key, sequence and mode; X: and the extra) into the survivors: their minima one at a
+// time, inserted the way the reference inserts, until none is left below the third survivor -- what is not below it cannot enter,
+// now or later in the round
+template <bool X> CTU_DEV void rs_round(rs_top3 &B, bool on, uint32_t khi, uint32_t klo, int seq, int mode, rs_extra x)
+{
+  for (int i = 0; i < 3; ++i) {
+    on = on && rs_key_lt(khi, klo, B.k[2]);
+    if (X) x.on = x.on && x.key < B.k[2];
+    const rs_pick pk = rs_pick_min<X>(on, khi, klo, seq, x);
+    if (pk.key == ~0ull) break;
+    rs_insert(B, pk.who < 64 ? __builtin_amdgcn_readlane(mode, pk.who) : x.mode, pk.key);
+    on = on && CTU_TID != pk.who;
+    if (X) x.on = x.on && pk.who != 64;
+  }
+}
+#endif
+
 // count_bits (search_intra.c:949-984)
 CTU_DEV double count_bits(const int8_t *preds, double planar, double not_planar, double mpm_bit, double not_mpm_bit, int mode)
 {
@@ -845,7 +940,94 @@ template <typename PX> CTU_DEV void mpm_neighbours(lds<PX> *S, int x, int y, int
   *above = (ly > 0 && y > 0) ? cu_at(S, lx + n - 1, ly - 1) : nullptr;
 }
 
-// search_intra_rough (search_intra.c:986-1229), three survivors; the winner goes to V->u_mode
+// search_intra_rough (search_intra.c:986-1229), three survivors; the winner goes to V->u_mode, its cost to V->rs_cand[0]
+#if defined(__HIPCC__)
+// Device: a lane per listed mode keeps the mode's cost in its registers and the three survivors are wave-uniform values -- the
+// minima of a round's newcomers are taken one at a time and inserted the way the reference inserts (rs_round), the
+// next round's list is derived in the lanes 0..5, a lane per try.  Only the list itself goes through LDS (rough_costs reads it).
+// The host emulation below keeps the general formulation through the LDS arrays; the two agree only if this one is right.
+template <typename PX> CTU_INLINE1 CTU_DEV void search_intra_rough(lds<PX> *S, const job<PX> &J, int x, int y, int lx, int ly, int n)
+{
+  wctx *const V = wv_of(S);
+  const params &P = J.P;
+  const int T = n >= 8 ? 8 : 4, tiles = (n / T) * (n / T);
+  const int lane = CTU_TID;
+  RQ_T0(J.W)
+  SERIAL {
+    const cu4 *l, *a;
+    mpm_neighbours(S, x, y, lx, ly, n, &l, &a);
+    dir_luma_predictor(y, V->mpm, l, a);
+  }
+  // round 0's list: planar, DC, every 2^levels-th angular mode from 2 + 2^levels / 2 (search_intra.c:1071-1143); the modes listed so
+  // far are a bit each of h0 : h1 : h2 (the same pattern in every word: 32 is a multiple of the step)
+  int offset = 1 << __builtin_amdgcn_readfirstlane(P.rough_levels);
+  const int first_m = 2 + offset / 2;
+  int nm = 2 + (66 - first_m) / offset + 1;
+  if (lane < nm) V->rs_list[lane] = lane < 2 ? lane : first_m + (lane - 2) * offset;
+  uint32_t pat = 1u << (first_m & (offset - 1));
+  for (int sh = offset; sh < 32; sh <<= 1) pat |= pat << sh;
+  uint32_t h0 = (pat & ~((1u << first_m) - 1u)) | 3u, h1 = pat, h2 = pat & 7u;
+  CTU_SYNC();
+  RQ_T(24);
+  CTU_LDS const uint32_t *const mdl = LDSP(const uint32_t, V->cur), *const part = LDSP(const uint32_t, V->part);
+  const double mpm_bit = m_fbits(mdl, M_MPM, 1), not_mpm_bit = m_fbits(mdl, M_MPM, 0);
+  const double planar = m_fbits(mdl, M_PLANAR + 1, 0), not_planar = m_fbits(mdl, M_PLANAR + 1, 1);
+  const rs_extra none = {false, 0, 0, 0};
+  rs_top3 B = {{0, 0, 0}, {~0ull, ~0ull, ~0ull}};
+  bool differs = false;
+  for (int round = 0;; ++round) {
+    rough_costs(S, J, lx, ly, n, V->rs_list, nm);
+    RQ_T(25);
+    bool on = lane < nm;
+    int mode = 0;
+    uint32_t khi = 0, klo = 0;
+    if (on) {                                   // a lane per mode: tile sums, bit cost
+      mode = V->rs_list[lane];
+      unsigned satd = 0, sad = 0;
+      for (int t = 0; t < tiles; ++t) { satd += part[2 * (lane * tiles + t)]; sad += part[2 * (lane * tiles + t) + 1]; }
+      if (n >= 8) satd >>= (px_info<PX>::depth - 8);       // satd_NxN shifts, the 4x4 function does not (picture-generic.c:170)
+      sad >>= (px_info<PX>::depth - 8);
+      double c = (double)(satd < sad * 2 ? satd : sad * 2);
+      c += count_bits(V->mpm, planar, not_planar, mpm_bit, not_mpm_bit, mode) * P.lambda_sqrt;
+      khi = (uint32_t)__double2hiint(c); klo = (uint32_t)__double2loint(c);
+    }
+    RQ_T(26);
+    // the newcomers in the order the reference inserts them: the list's order, DC ahead of planar (:1089-1106)
+    const int seq = (round == 0 && lane < 2) ? 1 - lane : lane;
+    if (round == 0)                             // min_cost != max_cost (:1082-1143): only the first round moves them
+      differs = __ballot(on && (khi != (uint32_t)__builtin_amdgcn_readlane((int)khi, 0) || klo != (uint32_t)__builtin_amdgcn_readlane((int)klo, 0))) != 0;
+    rs_round<false>(B, on, khi, klo, seq, mode, none);
+    // next round's list (search_intra.c:1146-1215): lane j tries b - off (j even) / b + off (j odd) of survivor j / 2; a mode is
+    // listed where it is first tried and only if it was never listed; a survivor outside 3..65 lists nothing
+    offset >>= 1;
+    if (!(offset > 0 && differs)) break;
+    int tu[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const int b = B.m[j >> 1], m = (j & 1) ? b + offset : b - offset;
+      tu[j] = (b >= 3 && b <= 65 && m >= 2 && m <= 66) ? m : -1;
+    }
+    const int t = lane == 0 ? tu[0] : lane == 1 ? tu[1] : lane == 2 ? tu[2] : lane == 3 ? tu[3] : lane == 4 ? tu[4] : lane == 5 ? tu[5] : -1;
+    bool listed = t >= 0 && !(((t < 32 ? h0 : (t < 64 ? h1 : h2)) >> (t & 31)) & 1u);
+#pragma unroll
+    for (int j = 0; j < 5; ++j) listed = listed && !(lane > j && tu[j] == t);
+    const unsigned long long lm = __ballot(listed);
+    if (listed) V->rs_list[__popcll(lm & ((1ull << lane) - 1ull))] = t;
+    nm = __popcll(lm);
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+      if (tu[j] >= 0) { const uint32_t bit = 1u << (tu[j] & 31); if (tu[j] < 32) h0 |= bit; else if (tu[j] < 64) h1 |= bit; else h2 |= bit; }
+    CTU_SYNC();
+    RQ_T(27);
+  }
+  SERIAL {
+    V->u_mode = B.m[0];
+    V->rs_cand[0] = __hiloint2double((int)(uint32_t)(B.k[0] >> 32), (int)(uint32_t)B.k[0]);
+  }
+  CTU_SYNC();
+  RQ_T(27);
+}
+#else
 template <typename PX> CTU_INLINE1 CTU_DEV void search_intra_rough(lds<PX> *S, const job<PX> &J, int x, int y, int lx, int ly, int n)
 {
   wctx *const V = wv_of(S);
@@ -944,6 +1126,8 @@ template <typename PX> CTU_INLINE1 CTU_DEV void search_intra_rough(lds<PX> *S, c
     if (V->u_d0 == 0) break;
   }
 }
+
+#endif
 
 // ---------------------------------------------------------------------------------------------------- transforms ------
 CTU_DEV const int16_t *dct2_matrix(int n) { return n == 4 ? VVC_DCT2_4 : n == 8 ? VVC_DCT2_8 : n == 16 ? VVC_DCT2_16 : VVC_DCT2_32; }

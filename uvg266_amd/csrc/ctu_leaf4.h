@@ -6,9 +6,13 @@
 // steps, four passes of prediction + SATD with three selections between them.  This file is the same arithmetic with the data where
 // a 4x4 block fits -- in the lanes' registers:
 //   * the 8x8 area's source samples are fetched from the picture ONCE per area (not three times per CU) and parked in LDS;
-//   * the rough search evaluates every angular mode in ONE pass, a lane per MODE (a lane predicts the whole 4x4 block and takes its
-//     Hadamard in registers); planar / DC run beside it on eight lanes.  The reference's three refinement rounds
-//     (search_intra.c:1071-1215) become selections over the finished cost table: a mode's cost does not depend on the round;
+//   * the rough search evaluates the angular modes 2..65 in ONE pass, lane L = mode L + 2 (a lane predicts the whole 4x4 block and
+//     takes its Hadamard in registers); planar / DC run beside it on eight lanes and stay two wave-uniform costs, mode 66 -- it
+//     can only be listed from a survivor at 62, 64 or 65 -- is costed on four lanes when it is first listed.  The reference's
+//     three refinement rounds (search_intra.c:1071-1215) become selections over the finished costs (a mode's cost does not depend
+//     on the round), made in the lanes that hold them: whether a mode is listed in a round and where in the order of insertion
+//     are predicates of its own lane on the wave-uniform survivors; the survivors are the minima under (cost, sequence), found by
+//     DPP reductions and inserted the way the reference inserts (ctu_core.h rs_round) -- no candidate list, no rank loop;
 //   * transforms: a lane per coefficient, the 4-point butterflies' operands fetched from the other lanes (ds_bpermute), no arrays;
 //   * uvg_rdoq (rdo.c:1449-1870) for the one coefficient group of a 4x4 block: a lane per position in RASTER order -- the context
 //     template's neighbours are the lanes +1, +2, +4, +5, +8 (DPP row shifts), the regular-bin budget a position sees is a
@@ -545,10 +549,10 @@ template <typename PX> CTU_INLINE1 CTU_DEV int leaf_rough(lds<PX> *S, const job<
     c_dc = rl64(c, 4);
   }
   LF_T(2);
-  // ---- pass A: lanes 2..63 = modes 4..65 (lanes 0, 1 idle along) ----
-  double cA;
+  // ---- pass A: lane L = mode L + 2 (modes 2..65); planar and DC stay the two wave-uniform costs above ----
+  uint32_t khi, klo;
   {
-    const int mode = lane < 2 ? 18 : lane + 2;
+    const int mode = lane + 2;
     const lf_mode M = leaf_mode(S, V, mode);
     int d[16];
 #pragma unroll
@@ -558,99 +562,75 @@ template <typename PX> CTU_INLINE1 CTU_DEV int leaf_rough(lds<PX> *S, const job<
 #pragma unroll
       for (int i = 0; i < 4; ++i) d[yd * 4 + i] = (M.vertical ? s[yd * 4 + i] : s[i * 4 + yd]) - out[i];
     }
-    cA = lf_cost<PX>(d, lf_count_bits(p0, p1, p2, p3, p4, p5, planar, not_planar, mpm_bit, not_mpm_bit, mode), P.lambda_sqrt);
+    const double cA = lf_cost<PX>(d, lf_count_bits(p0, p1, p2, p3, p4, p5, planar, not_planar, mpm_bit, not_mpm_bit, mode), P.lambda_sqrt);
+    khi = (uint32_t)__double2hiint(cA); klo = (uint32_t)__double2loint(cA);
   }
-  cA = lane == 0 ? c_planar : (lane == 1 ? c_dc : cA);
   LF_T(3);
-  // cost of a (wave-uniform) mode: pass A's lanes, or pass B's (lanes 0..2 = modes 2, 3, 66)
-  double cB = 0;
-#define LF_LANE_A(m) ((m) < 2 ? (m) : (m) - 2)
-#define LF_IN_B(m) ((m) == 2 || (m) == 3 || (m) == 66)
-#define LF_LANE_B(m) ((m) == 66 ? 2 : (m) - 2)
-#define LF_COST(m) (LF_IN_B(m) ? rl64(cB, LF_LANE_B(m)) : rl64(cA, LF_LANE_A(m)))
-  // ---- round 0: planar, DC, every 2^levels-th angular mode (search_intra.c:1071-1143) ----
-  // The reference's three-entry list under strict "<" insertion = the three smallest under (cost, insertion sequence); DC is inserted
-  // ahead of planar when the two tie (:1089-1106).  Candidates sit one per lane: (mode, cost, sequence); a lane counts who is ahead of it.
+  // ---- the rounds (search_intra.c:1071-1215) as selections over the finished costs, every mode judged in its own lane ----
+  // The reference's three-entry list under strict "<" insertion = the three smallest of everything listed so far under (cost,
+  // insertion sequence).  Per round the newly listed modes' minima are taken one at a time and inserted into the sorted list of
+  // survivors the way the reference inserts (rs_round).
+  // Round 0 lists DC, then planar (:1089-1106), then every 2^levels-th angular mode in ascending order.  Its first angular mode
+  // is 4 or 6, so DC and planar ride in the lanes 0 and 1 for this round: ascending lane order is the order of insertion.
   const int levels = __builtin_amdgcn_readfirstlane(P.rough_levels);
   int offset = 1 << levels;
-  const int first_m = 2 + offset / 2;                                   // listed angular modes: first_m + k * offset <= 66
-  int ncand = 2 + (66 - first_m) / offset + 1;
-  int cm = lane < 2 ? lane : first_m + (lane - 2) * offset, cseq = lane == 0 ? 1 : (lane == 1 ? 0 : 3 + lane);
-  if (lane >= ncand) cm = 0;
-  double cc;
+  const int first_m = 2 + offset / 2;                                   // listed angular modes: first_m + k * offset (never 66)
+  bool seen = lane + 2 >= first_m && ((lane + 2 - first_m) & (offset - 1)) == 0, seen66 = false;    // modes listed so far: a flag in the mode's own lane; mode 66's is wave-uniform
+  rs_top3 B = {{0, 0, 0}, {~0ull, ~0ull, ~0ull}};
+  const rs_extra none = {false, 0, 0, 0};
+  bool differs;
   {
-    const int src = LF_LANE_A(cm);                                      // (round 0 never lists a mode of pass B: first_m >= 4)
-    cc = __hiloint2double(lf_shfl(__double2hiint(cA), src), lf_shfl(__double2loint(cA), src));
+    const uint64_t kd = rs_key(c_dc), kp = rs_key(c_planar);
+    const uint32_t ch = lane == 0 ? (uint32_t)(kd >> 32) : lane == 1 ? (uint32_t)(kp >> 32) : khi, cl = lane == 0 ? (uint32_t)kd : lane == 1 ? (uint32_t)kp : klo;
+    const bool on = seen || lane < 2;
+    // min_cost != max_cost (:1082-1143): only the first round moves them
+    differs = __ballot(on && (ch != (uint32_t)(kp >> 32) || cl != (uint32_t)kp)) != 0;
+    rs_round<false>(B, on, ch, cl, lane, lane < 2 ? 1 - lane : lane + 2, none);
   }
-  // modes costed so far: a flag in the mode's own lane of pass A / pass B
-  int seenA = (lane < 2 || (lane + 2 >= first_m && ((lane + 2 - first_m) & (offset - 1)) == 0)) ? 1 : 0, seenB = 0;
-  int b0, b1, b2;
-  double k0, k1, k2;
-  bool have_B = false;
-  bool differs = false;
-  for (int round = 0;; ++round) {
-    // rank of every candidate
-    int rank = 0;
-    for (int j = 0; j < ncand; ++j) {
-      const double o = rl64(cc, j);
-      const int oseq = __builtin_amdgcn_readlane(cseq, j);
-      rank += (o < cc || (o == cc && oseq < cseq)) ? 1 : 0;
-    }
-    const bool in = lane < ncand;
-    if (round == 0) differs = __ballot(in && cc != rl64(cc, 0)) != 0;      // min_cost != max_cost (:1082-1143): only the first round moves them
-    const int w0 = __builtin_ctzll(__ballot(in && rank == 0)), w1 = __builtin_ctzll(__ballot(in && rank == 1)), w2 = __builtin_ctzll(__ballot(in && rank == 2));
-    b0 = __builtin_amdgcn_readlane(cm, w0); b1 = __builtin_amdgcn_readlane(cm, w1); b2 = __builtin_amdgcn_readlane(cm, w2);
-    k0 = rl64(cc, w0); k1 = rl64(cc, w1); k2 = rl64(cc, w2);
-    // next round's list (search_intra.c:1146-1215)
+  for (;;) {
+    // next round's list (search_intra.c:1146-1215): b - off, b + off of the three survivors in rank order, a mode where it is
+    // first tried and only if it was never listed; a survivor outside 3..65 lists nothing.  The try's index is the sequence.
     const int off = offset >> 1;
     if (!(off > 0 && differs)) break;
-    if (!have_B) {
-      // (2, 3, 66 can only be listed from a survivor within 4 of them: 2 + off, 3 +- off, 66 - off with off <= 4)
-#define LF_EDGE(b) (((b) >= 2 && (b) <= 7) || (b) >= 62)
-      const bool edge = LF_EDGE(b0) || LF_EDGE(b1) || LF_EDGE(b2);
-#undef LF_EDGE
-      if (edge) {
-        const int mode = lane == 0 ? 2 : (lane == 1 ? 3 : 66);
-        const lf_mode M = leaf_mode(S, V, mode);
-        int d[16];
+    int t[6];
 #pragma unroll
-        for (int yd = 0; yd < 4; ++yd) {
-          int out[4];
-          leaf_ang_row<PX, false>(S, M, yd, out);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) d[yd * 4 + i] = (M.vertical ? s[yd * 4 + i] : s[i * 4 + yd]) - out[i];
-        }
-        cB = lf_cost<PX>(d, lf_count_bits(p0, p1, p2, p3, p4, p5, planar, not_planar, mpm_bit, not_mpm_bit, mode), P.lambda_sqrt);
-        have_B = true;
-      }
+    for (int j = 0; j < 6; ++j) {
+      const int b = B.m[j >> 1], m = (j & 1) ? b + off : b - off;
+      t[j] = (b >= 3 && b <= 65 && m >= 2 && m <= 66) ? m : -1;
     }
-    // survivors in lanes 0..2 (sequence 0..2), the new modes behind them (sequence 3 + index): written lane by lane from scalars
-    int cclo = __double2loint(cc), cchi = __double2hiint(cc);
-#define LF_PUT(ln, m_, c_) do { const double c__ = (c_); const bool me__ = lane == (ln); cm = me__ ? (m_) : cm; cclo = me__ ? __double2loint(c__) : cclo; \
-      cchi = me__ ? __double2hiint(c__) : cchi; } while (0)
-    LF_PUT(0, b0, k0); LF_PUT(1, b1, k1); LF_PUT(2, b2, k2);
-    int n_new = 0;
-#define LF_TRY(m_) do { const int m = (m_); if (m >= 2 && m <= 66) { const bool inb = LF_IN_B(m); const int ln = inb ? LF_LANE_B(m) : LF_LANE_A(m); \
-      const int was = inb ? __builtin_amdgcn_readlane(seenB, ln) : __builtin_amdgcn_readlane(seenA, ln); \
-      if (!was) { if (inb) { seenB = lane == ln ? 1 : seenB; LF_PUT(3 + n_new, m, rl64(cB, ln)); } \
-                  else { seenA = lane == ln ? 1 : seenA; LF_PUT(3 + n_new, m, rl64(cA, ln)); } ++n_new; } } } while (0)
-    if (b0 >= 3 && b0 <= 65) { LF_TRY(b0 - off); LF_TRY(b0 + off); }
-    if (b1 >= 3 && b1 <= 65) { LF_TRY(b1 - off); LF_TRY(b1 + off); }
-    if (b2 >= 3 && b2 <= 65) { LF_TRY(b2 - off); LF_TRY(b2 + off); }
-#undef LF_TRY
-#undef LF_PUT
-    cc = __hiloint2double(cchi, cclo);
-    ncand = 3 + n_new;
-    cseq = lane;
+    int seq = -1, seq66 = -1;
+#pragma unroll
+    for (int j = 5; j >= 0; --j) { seq = t[j] == lane + 2 ? j : seq; seq66 = t[j] == 66 ? j : seq66; }
+    const bool on = seq >= 0 && !seen;
+    seen = seen || on;
+    rs_extra x0 = {seq66 >= 0 && !seen66, 0, seq66, 66};
+    if (x0.on) {
+      // mode 66 does not fit the 64 lanes; it is listed from a survivor at 62, 64 or 65 only: four lanes, a row each
+      LF_T(4);
+      seen66 = true;
+      const int r = lane & 3;
+      const lf_mode M = leaf_mode(S, V, 66);
+      int out[4], d[4], sad = 0;
+      leaf_ang_row<PX, false>(S, M, r, out);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int sv = r == 0 ? s[i] : r == 1 ? s[4 + i] : r == 2 ? s[8 + i] : s[12 + i];
+        d[i] = sv - out[i];
+        sad += iabs_(d[i]);
+      }
+      const int satd = satd4_cost(d, r);
+      sad = dpp_group_sum<4>(sad);
+      sad >>= (px_info<PX>::depth - 8);
+      const double c = (double)(satd < sad * 2 ? satd : sad * 2) + lf_count_bits(p0, p1, p2, p3, p4, p5, planar, not_planar, mpm_bit, not_mpm_bit, 66) * P.lambda_sqrt;
+      x0.key = rs_key(rl64(c, 0));
+      LF_TN(10);
+      rs_round<true>(B, on, khi, klo, seq, lane + 2, x0);
+    } else
+      rs_round<false>(B, on, khi, klo, seq, lane + 2, none);
     offset = off;
   }
-#undef LF_LANE_A
-#undef LF_IN_B
-#undef LF_LANE_B
-#undef LF_COST
-  (void)k0; (void)k1; (void)k2; (void)b1; (void)b2;
   LF_T(4);
-  return b0;
+  return B.m[0];
 }
 
 // ---- transforms ------------------------------------------------------------------------------------------------------------------
