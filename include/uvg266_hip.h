@@ -986,6 +986,55 @@ UVGHIP_API int uvghip_loop_plan_results(const uvghip_loop_plan_t *plan, const in
  * bytes (row r of picture p at rows + (p * n_rows + r) * row_cap) and their lengths ([picture][row]). */
 UVGHIP_API int uvghip_loop_plan_slice_data(const uvghip_loop_plan_t *plan, const uint8_t **rows, const int32_t **row_bytes, int *row_cap,
                                            int *n_rows);
+
+/* The loop plan of a BAND of CTU rows [ctu_row0, ctu_row1) of every picture: one picture sharded over the GPUs of a node by CTU rows
+ * with the closed loop whole -- search (uvghip_ctu_plan_create_rows), filter stage and coder over the band's rows only.  The hand-over
+ * goes ONE way: the per-CTU filter stage pulls (a CTU builds its tile from the unfiltered reconstruction of itself and its left, upper
+ * and upper-left neighbour and writes only up and left of its lower right corner), the SAO decision chains from the left and from the
+ * first CTU of the row above, and every WPP row's substream starts from the models behind the first CTU of the row above -- so a band
+ * reads of the band ABOVE and of nothing below.  The band's rows of every output come out as the whole-picture plan gives them
+ * (tests/test_gpu_loop_bands.py: against the reference encoder's records).
+ * uvghip_loop_plan_create is the call with (0, CTU rows of the picture) and sao_type 1..3; this call also takes sao_type 0 (no SAO:
+ * out = the deblocked picture, no SAO syntax in the rows).  Same workspace size, same accessors; uvghip_loop_plan_slice_data keeps
+ * its layout (row r of a picture at its usual place; rows outside the band are not written).  uvghip_loop_plan_run, _run_search and
+ * _run_filters work on a band plan; uvghip_loop_plan_run_overlapped on a band plan IS uvghip_loop_plan_run.  The filter launch knows
+ * the band's first row: no CTU waits for a flag of a row outside the band.
+ *
+ * The hand-over.  Before a run of a band with ctu_row0 > 0 the caller puts into the plan's buffers what the band's three launches read
+ * of the band above; after the run of a band with ctu_row1 < CTU rows it takes the same pieces out of that band's buffers.
+ * uvghip_loop_plan_halo lists them for all pictures -- side 0: received from above, side 1: sent down -- as (device pointer, bytes per
+ * row, rows, pitch in bytes); cap < the number of pieces is an error, *n reports the need either way.  The list goes kind after kind,
+ * inside a kind picture after picture.  The kinds, with Y = 64 * the boundary's CTU row, b = bytes per sample, wc = CTUs per row:
+ *   rec_y rows [Y - 16, Y), rec_u / rec_v rows [Y / 2 - 8, Y / 2): the unfiltered reconstruction the first row's tiles start in (the
+ *     search's single line is the last of them);
+ *   cu rows [Y / 4 - 4, Y / 4) of wc * 16 units: the tiles' edges and filter strengths, the search's and the coder's contexts;
+ *   with SAO: the deblocked picture (in the workspace) luma rows [Y - 11, Y - 8), chroma rows [Y / 2 - 6, Y / 2 - 4): what the first
+ *     row's part of the output picture reads above the band's own deblocked rows (10 rows of SAO delay, one more for the edge classes);
+ *   with SAO: the decisions of the whole CTU row above (wc * 34 int32): merge candidates, and the offsets of the 10 output rows above;
+ *   the third model set of the FIRST CTU of the row above (UVGHIP_CTU_MODELS uint32): the WPP hand-over of search and coder;
+ *   with SAO: the SAO models behind that CTU (6 uint16).
+ * uvghip_loop_plan_halo_bytes: the size of ONE packed message = n_pictures * (b * 24 * pic_w + 2048 * wc + 4 * UVGHIP_CTU_MODELS +
+ * (sao_type ? b * 5 * pic_w + 136 * wc + 12 : 0)) -- the pieces' bytes, nothing else; 0 for a plan of the whole picture.  The message
+ * holds piece kind after piece kind in the order above, inside a kind picture after picture, rows tightly packed: its layout depends on
+ * (bitdepth, n_pictures, pic_w, sao_type) only, not on strides, so two bands whose planes are padded differently agree.
+ * uvghip_loop_plan_halo_pack gathers the side 1 pieces of all pictures into `message` (device memory) in ONE launch,
+ * uvghip_loop_plan_halo_unpack scatters a message into the side 0 pieces: a boundary costs one send and one receive per group.
+ * uvghip_loop_plan_out_rows: the luma rows [*y0, *y1) of the output pictures the band writes: [ctu_row0 ? 64 ctu_row0 - delay : 0,
+ * last band ? pic_h : 64 ctu_row1 - delay), delay = 10 (8 with sao_type 0).  The bands' rectangles tile the picture, so their
+ * uvghip_picture_checksum_rect terms add up to the picture's checksum. */
+typedef struct uvghip_halo_piece {
+  void *ptr;                 /* DEVICE: the piece's first row */
+  size_t row_bytes, pitch;   /* bytes of a row that belong to the piece; distance of two rows */
+  int32_t rows, reserved;
+} uvghip_halo_piece_t;
+UVGHIP_API int uvghip_loop_plan_create_rows(int bitdepth, const uvghip_ctu_params_t *params, const uvghip_loop_picture_t *pictures,
+                                            int n_pictures, int sao_type, int ctu_row0, int ctu_row1, void *workspace,
+                                            uvghip_loop_plan_t **plan_out);
+UVGHIP_API int uvghip_loop_plan_halo(const uvghip_loop_plan_t *plan, int side, uvghip_halo_piece_t *pieces, int cap, int *n);
+UVGHIP_API size_t uvghip_loop_plan_halo_bytes(const uvghip_loop_plan_t *plan);
+UVGHIP_API int uvghip_loop_plan_halo_pack(uvghip_loop_plan_t *plan, void *message, void *stream);
+UVGHIP_API int uvghip_loop_plan_halo_unpack(uvghip_loop_plan_t *plan, const void *message, void *stream);
+UVGHIP_API int uvghip_loop_plan_out_rows(const uvghip_loop_plan_t *plan, int *y0, int *y1);
 UVGHIP_API void uvghip_loop_plan_destroy(uvghip_loop_plan_t *plan);
 
 /* ------------------- (6) the slice data: the arithmetic coder on the device -------------------------------------------- */

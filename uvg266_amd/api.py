@@ -616,9 +616,10 @@ class CtuSearch:
     src: list of (y, u, v) device planes.  Outputs stay on the device: rec[i] = (y, u, v), cu[i] (uvghip_scu_t table as bytes,
     [rows of 4x4, 16 * CTUs per row, 32]), coeff[i] ([CTUs, 6144] int16), models[i] ([CTUs, 3, 257] uint32 as int32)."""
 
-    def __init__(self, params, src, _make_plan=True, rows=None):
+    def __init__(self, params, src, _make_plan=True, rows=None, _pad=0):
         """rows = (ctu_row0, ctu_row1): search only that band of CTU rows of every picture (uvghip_ctu_plan_create_rows; the caller
-        provides the halo of the row above in rec / cu / models, bands.BandLayout.halo_search)."""
+        provides the halo of the row above in rec / cu / models, bands.BandLayout.halo_search).  _pad: the reconstruction planes get a
+        stride of that many samples more than the width (rec_full holds the whole allocations)."""
         self.P = params
         self.n = len(src)
         W, H = params.pic_w, params.pic_h
@@ -627,14 +628,15 @@ class CtuSearch:
         self.depth = _depth(src[0][0])
         self.L = _lib.init(dev.index or 0)
         self.src = src
-        self.rec = [tuple(torch.zeros_like(p) for p in s) for s in src]
+        self.rec_full = [tuple(torch.zeros((p.shape[0], p.shape[1] + _pad), dtype=p.dtype, device=dev) for p in s) for s in src]
+        self.rec = [tuple(f[:, :p.shape[1]] for f, p in zip(fs, s)) for fs, s in zip(self.rec_full, src)]
         ctus = self.wc * self.hc
         self.cu = [torch.zeros((self.hc * 16, self.wc * 16, 32), dtype=torch.uint8, device=dev) for _ in src]
         self.coeff = [torch.zeros((ctus, 6144), dtype=torch.int16, device=dev) for _ in src]
         self.models = [torch.zeros((ctus, 3, 257), dtype=torch.int32, device=dev) for _ in src]
         self.pics = (_lib.CtuPicture * self.n)()
         for i, (s, r) in enumerate(zip(src, self.rec)):
-            self.pics[i] = _lib.CtuPicture(_dev(s[0]), _dev(s[1]), _dev(s[2]), s[0].stride(0), s[1].stride(0), _dev(r[0]), _dev(r[1]), _dev(r[2]),
+            self.pics[i] = _lib.CtuPicture(_dev(s[0]), _dev(s[1]), _dev(s[2]), s[0].stride(0), s[1].stride(0), r[0].data_ptr(), r[1].data_ptr(), r[2].data_ptr(),
                                            r[0].stride(0), r[1].stride(0), _dev(self.cu[i]), self.wc * 16, 0, _dev(self.coeff[i]), _dev(self.models[i]))
 
         self.plan = None
@@ -718,23 +720,118 @@ class FramePool:
 class ClosedLoop(CtuSearch):
     """uvghip_loop_plan_*: the search of CtuSearch followed by the in-loop filters on the reference's schedule, one call per
     group of pictures.  Adds out[i] = (y, u, v), the pictures after deblocking + SAO, and after a run sao_info ([n, ctus, 2, 17]
-    int32) / sao_models ([n, ctus, 6] as int16 storage of uint16) as device tensors over the plan's own buffers."""
+    int32) / sao_models ([n, ctus, 6] as int16 storage of uint16) as device tensors over the plan's own buffers.
 
-    def __init__(self, params, src, sao_type=3):
+    rows = (ctu_row0, ctu_row1): the loop of that band of CTU rows of every picture (uvghip_loop_plan_create_rows) -- one picture sharded
+    over devices by CTU rows.  Before run() the band takes what it reads of the band above (halo(0), or halo_unpack of the upper band's
+    halo_pack message); it writes the rows out_rows() of the output pictures, its CTU rows of the decisions and its rows of the slice
+    data; substreams() is its contribution to the pictures' NAL units (bands.gather_band_nals).  sao_type 0 (no SAO) goes the same way.
+    pad: the reconstruction and output planes get a stride of that many samples more than the width (rec_full / out_full)."""
+
+    def __init__(self, params, src, sao_type=3, rows=None, pad=0, prepare=None):
+        """prepare(loop): called when every buffer exists and before the plan is created (the tests poison the buffers and the workspace)."""
         import ctypes
-        super().__init__(params, src, _make_plan=False)
+        super().__init__(params, src, _make_plan=False, _pad=pad)
         dev = src[0][0].device
-        self.out = [tuple(torch.empty_like(p) for p in s) for s in src]
+        self.sao_type = sao_type
+        self.out_full = [tuple(torch.empty((p.shape[0], p.shape[1] + pad), dtype=p.dtype, device=dev) for p in s) for s in src]
+        self.out = [tuple(f[:, :p.shape[1]] for f, p in zip(fs, s)) for fs, s in zip(self.out_full, src)]
         W, H = params.pic_w, params.pic_h
         self.loop_ws = torch.empty(self.L.uvghip_loop_workspace_bytes(self.depth, self.n, W, H), dtype=torch.uint8, device=dev)
         lp = (_lib.LoopPicture * self.n)()
         for i in range(self.n):
             o = self.out[i]
-            lp[i] = _lib.LoopPicture(self.pics[i], _dev(o[0]), _dev(o[1]), _dev(o[2]), o[0].stride(0), o[1].stride(0))
+            lp[i] = _lib.LoopPicture(self.pics[i], o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), o[0].stride(0), o[1].stride(0))
         self.loop_pics = lp
         self.loop = ctypes.c_void_p()
-        _lib.check(self.L.uvghip_loop_plan_create(self.depth, ctypes.byref(self.P), lp, self.n, sao_type, _dev(self.loop_ws), ctypes.byref(self.loop)),
-                   "uvghip_loop_plan_create")
+        if prepare is not None:
+            prepare(self)
+        if rows is None and sao_type != 0:
+            _lib.check(self.L.uvghip_loop_plan_create(self.depth, ctypes.byref(self.P), lp, self.n, sao_type, _dev(self.loop_ws), ctypes.byref(self.loop)),
+                       "uvghip_loop_plan_create")
+        else:
+            r0, r1 = (0, self.hc) if rows is None else rows
+            _lib.check(self.L.uvghip_loop_plan_create_rows(self.depth, ctypes.byref(self.P), lp, self.n, sao_type, int(r0), int(r1), _dev(self.loop_ws),
+                                                           ctypes.byref(self.loop)), "uvghip_loop_plan_create_rows")
+
+    # ---- a band's hand-over (uvghip_loop_plan_halo*) ----
+    def halo_pieces(self, side):
+        """uvghip_loop_plan_halo: [(device pointer, bytes per row, rows, pitch in bytes)] of all pictures -- side 0: what the band receives
+        from the band above, side 1: what it sends to the band below."""
+        import ctypes
+        n = ctypes.c_int(0)
+        self.L.uvghip_loop_plan_halo(self.loop, side, None, 0, ctypes.byref(n))          # (the need; an error if there are pieces)
+        arr = (_lib.HaloPiece * max(1, n.value))()
+        _lib.check(self.L.uvghip_loop_plan_halo(self.loop, side, arr, n.value, ctypes.byref(n)), "uvghip_loop_plan_halo")
+        return [(int(a.ptr), int(a.row_bytes), int(a.rows), int(a.pitch)) for a in arr[:n.value]]
+
+    def halo(self, side):
+        """The same pieces as exchange-list entries (tensor, row0, row1) for bands.emulate / the transports: every piece as rows of a 2-D byte
+        view [rows, bytes per row] over the buffer it lies in, at the piece's pitch -- row indices are the piece's own coordinates (picture
+        rows of a plane, unit rows of cu, model sets, CTU rows of the decisions), so two bands' lists pair up whatever their strides."""
+        owners = [f for fs in self.rec_full for f in fs] + self.cu + self.models + [self.loop_ws]
+        flat = [(o.data_ptr(), o.numel() * o.element_size(), o.view(torch.uint8).reshape(-1)) for o in owners]
+        out = []
+        for ptr, row_bytes, rows, pitch in self.halo_pieces(side):
+            base, size, t = next(f for f in flat if f[0] <= ptr < f[0] + f[1])
+            off = ptr - base
+            r0, col = off // pitch, off % pitch
+            assert (r0 + rows - 1) * pitch + col + row_bytes <= size, "a piece ends outside its buffer"
+            out.append((torch.as_strided(t, (r0 + rows, row_bytes), (pitch, 1), t.storage_offset() + col), r0, r0 + rows))
+        return out
+
+    def halo_ops(self, up=None, down=None):
+        """The exchange list of the band: receive halo(0) from rank `up`, send halo(1) to rank `down` (None: no such neighbour)."""
+        ops = []
+        if up is not None:
+            ops.append((up, [], self.halo(0)))
+        if down is not None:
+            ops.append((down, self.halo(1), []))
+        return ops
+
+    def halo_bytes(self):
+        return int(self.L.uvghip_loop_plan_halo_bytes(self.loop))
+
+    def halo_pack(self, message=None, stream=None):
+        """uvghip_loop_plan_halo_pack: everything the band below reads of this band, of all pictures, into one contiguous device buffer
+        (uint8 [halo_bytes()]) in one launch -> the message."""
+        if message is None:
+            message = torch.empty(self.halo_bytes(), dtype=torch.uint8, device=self.loop_ws.device)
+        assert message.numel() * message.element_size() >= self.halo_bytes()
+        _lib.check(self.L.uvghip_loop_plan_halo_pack(self.loop, _dev(message), _stream() if stream is None else stream), "uvghip_loop_plan_halo_pack")
+        return message
+
+    def halo_unpack(self, message, stream=None):
+        """uvghip_loop_plan_halo_unpack: the upper band's message into this band's buffers, one launch."""
+        assert message.numel() * message.element_size() >= self.halo_bytes()
+        _lib.check(self.L.uvghip_loop_plan_halo_unpack(self.loop, _dev(message), _stream() if stream is None else stream), "uvghip_loop_plan_halo_unpack")
+
+    def out_rows(self):
+        """uvghip_loop_plan_out_rows -> (y0, y1): the luma rows of the output pictures this plan writes."""
+        import ctypes
+        a, b = ctypes.c_int(), ctypes.c_int()
+        _lib.check(self.L.uvghip_loop_plan_out_rows(self.loop, ctypes.byref(a), ctypes.byref(b)), "uvghip_loop_plan_out_rows")
+        return a.value, b.value
+
+    def substreams(self, rows=None):
+        """What this plan contributes to the NAL units of its pictures after run(), in tiles.write_nals' form: (lens [n, CTU rows] int32 -- 0
+        for the rows of other bands --, the owned rows' bytes one after the other (uint8), sums [n, 3] uint32: the checksum terms of the
+        rows out_rows() of the output pictures, uvghip_picture_checksum_rect).  Over the bands lengths and sums add up.  rows: the plan's CTU
+        rows (ctu_row0, ctu_row1); None: all."""
+        r0, r1 = (0, self.hc) if rows is None else rows
+        y0, y1 = self.out_rows()
+        W = int(self.P.pic_w)
+        sums = torch.zeros((self.n, 4), dtype=torch.int32, device=self.loop_ws.device)
+        for i, o in enumerate(self.out):
+            _lib.check(self.L.uvghip_picture_checksum_rect(self.depth, o[0].data_ptr(), o[0].stride(0), o[1].data_ptr(), o[2].data_ptr(), o[1].stride(0), 0, y0, W, y1 - y0,
+                                                           _dev(sums[i]), _stream()), "uvghip_picture_checksum_rect")
+        data, nb = self.slice_data()
+        nb = nb.cpu().numpy()
+        data = data.cpu().numpy()
+        lens = np.zeros((self.n, self.hc), np.int32)
+        lens[:, r0:r1] = nb[:, r0:r1]
+        parts = [data[i, r, :lens[i, r]] for i in range(self.n) for r in range(r0, r1)]
+        return lens, np.concatenate(parts) if parts else np.zeros(0, np.uint8), sums[:, :3].cpu().numpy().view(np.uint32)
 
     def run(self, stream=None):
         """Enqueue search + filters of all n pictures (uvghip_loop_plan_run); returns at once."""

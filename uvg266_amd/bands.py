@@ -81,6 +81,31 @@ class BandLayout:
             ops.append((self.down, [self._rows(y, b - 1, b, 1), (u, b // 2 - 1, b // 2), (v, b // 2 - 1, b // 2), (scu, b // 4 - 1, b // 4), (models, k, k + 1)], []))
         return ops
 
+    def halo_loop(self, y, u, v, scu, models, dbk_y, dbk_u, dbk_v, sao_info, sao_models, ctus_per_row, sao_type=3):
+        """The closed loop of a band (uvghip_loop_plan_create_rows: search, filter stage, coder) reads of the band above, and of nothing
+        below -- one direction, sent down after the band has run, received before the band starts:
+          the 16 luma / 8 chroma lines of the unfiltered reconstruction its first row's filter tiles start in (y, u, v: the search's
+          single line is the last of them); 4 rows of per-4x4 side information (scu: [unit rows, bytes]); the models behind the FIRST CTU of
+          the row above (models: [3 * CTUs, words], row 3 k + 2 = the third set of CTU k); and with SAO the deblocked lines the first output
+          rows read above the band's own (dbk_*: luma 11 .. 9 above the boundary, chroma 6 .. 5), the decisions of the whole CTU row above
+          (sao_info: [CTU rows, words]) and the SAO models behind its first CTU (sao_models: [CTUs, words]).
+        The same pieces, in the same order, as uvghip_loop_plan_halo lists for one picture; their bytes are halo_loop_bytes()."""
+        def pieces(b):          # at the boundary above CTU row b
+            Y, k = 64 * b, (b - 1) * ctus_per_row
+            p = [(y, Y - 16, Y), (u, Y // 2 - 8, Y // 2), (v, Y // 2 - 8, Y // 2), (scu, Y // 4 - 4, Y // 4)]
+            if sao_type:
+                p += [(dbk_y, Y - 11, Y - 8), (dbk_u, Y // 2 - 6, Y // 2 - 4), (dbk_v, Y // 2 - 6, Y // 2 - 4), (sao_info, b - 1, b)]
+            p.append((models, 3 * k + 2, 3 * k + 3))
+            if sao_type:
+                p.append((sao_models, k, k + 1))
+            return p
+        ops = []
+        if self.up >= 0:
+            ops.append((self.up, [], pieces(self.ctu_row0)))
+        if self.down >= 0:
+            ops.append((self.down, pieces(self.ctu_row1), []))
+        return ops
+
     def halo_alf(self, y, u, v):
         """After SAO: ALF classification, filtering and statistics of a band read 3 rows of SAO output across either
         boundary (clamped at the virtual boundary, src/alf.h:32-33); 4 luma / 2 chroma rows are exchanged."""
@@ -106,6 +131,22 @@ class BandLayout:
             ops.append((peer, [self._rows(p, self.y0, self.y1, s) for p, s in ((y, 1), (u, 2), (v, 2))],
                         [self._rows(p, other.y0, other.y1, s) for p, s in ((y, 1), (u, 2), (v, 2))]))
         return ops
+
+
+def halo_loop_bytes(bitdepth, n_pictures, pic_w, sao_type=3):
+    """The bytes of one boundary's hand-over of the closed loop (uvghip_loop_plan_halo_bytes; include/uvg266_hip.h): per picture the 16 + 8 +
+    8 lines of reconstruction, 4 rows of 32-byte units, 257 models, and with SAO 3 + 2 + 2 deblocked lines, 34 words per CTU of the row
+    and 6 half-words."""
+    b, wc = (1 if bitdepth == 8 else 2), (pic_w + 63) // 64
+    return n_pictures * (b * 24 * pic_w + 2048 * wc + 4 * 257 + ((b * 5 * pic_w + 136 * wc + 12) if sao_type else 0))
+
+
+def gather_band_nals(loop, rows, first_poc=0, group=None, dst=0):
+    """The NAL units of the pictures of a group whose CTU rows are sharded over the ranks of `group`: every rank contributes the slice rows
+    of its band `rows` = (ctu_row0, ctu_row1) and the checksum terms of the output rows it wrote (api.ClosedLoop.substreams); rank `dst`
+    writes the pictures' NAL units (uvghip_write_picture_nals, a host function).  Collective; -> list of bytes on `dst`, None elsewhere."""
+    from . import tiles
+    return tiles.gather_nals(loop.substreams(rows), first_poc, sao=loop.sao_type != 0, group=group, dst=dst)
 
 
 def _nbytes(entry):

@@ -44,6 +44,8 @@ struct filt_ctu {                         // one CTU's job
   const uvghip_scu_t *scu;
   int32_t scu_stride;
   int32_t W, H, cx, cy, wc, hc;
+  int32_t row0;                           // first CTU row of the launch (a band of CTU rows; else 0): the row above it is complete in the buffers -- its
+                                          // flags are never waited for, its samples, decisions and models are read as they lie
   int32_t *sao_done, *final_done;         // this picture's flags [ctus]
 };
 
@@ -242,7 +244,7 @@ __device__ CTUF_CALL void filter_ctu(unsigned char *smem, const filt_pic &P, con
     __syncthreads();
   }
   // ---- the decision ----
-  const int32_t *left_f = cx ? &J.sao_done[k - 1] : nullptr, *top_f = cy ? &J.sao_done[k - wc] : nullptr;
+  const int32_t *left_f = cx ? &J.sao_done[k - 1] : nullptr, *top_f = cy > J.row0 ? &J.sao_done[k - wc] : nullptr;
   if (P.sao_type) {
     if (threadIdx.x < 2) {
       const int g = threadIdx.x;
@@ -297,8 +299,8 @@ __device__ CTUF_CALL void filter_ctu(unsigned char *smem, const filt_pic &P, con
   __syncthreads();
   if (threadIdx.x == 0) {
     if (cx) wait_set(&J.final_done[k - 1]);
-    if (cy) wait_set(&J.final_done[k - wc]);
-    if (cy && cx + 1 < wc) wait_set(&J.final_done[k - wc + 1]);
+    if (cy > J.row0) wait_set(&J.final_done[k - wc]);
+    if (cy > J.row0 && cx + 1 < wc) wait_set(&J.final_done[k - wc + 1]);
     __hip_atomic_store(&J.final_done[k], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
   }
   __syncthreads();

@@ -157,7 +157,7 @@ __global__ void __launch_bounds__(NT) ctu_search_pb_kernel(pb_launch_args A)
       F.rec_y = D.rec_y; F.rec_u = D.rec_u; F.rec_v = D.rec_v; F.src_y = D.src_y; F.src_u = D.src_u; F.src_v = D.src_v;
       F.rec_stride = D.rec_stride; F.rec_stride_c = D.rec_stride_c; F.src_stride = D.src_stride; F.src_stride_c = D.src_stride_c;
       F.scu = D.cu; F.scu_stride = D.cu_stride;
-      F.W = D.P.pic_w; F.H = D.P.pic_h; F.cx = cx; F.cy = cy; F.wc = A.wc; F.hc = A.hc;
+      F.W = D.P.pic_w; F.H = D.P.pic_h; F.cx = cx; F.cy = cy; F.wc = A.wc; F.hc = A.hc; F.row0 = 0;
       F.sao_done = A.sao_done + (size_t)pic * ctus; F.final_done = A.final_done + (size_t)pic * ctus;
       ctuf::filter_ctu<PX>(smem, A.fpics[pic], F);
       if (threadIdx.x == 0) S->rot = 0;

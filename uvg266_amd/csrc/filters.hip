@@ -14,6 +14,7 @@
 #include "uvghip_common.h"
 #define CTUF_CALL __attribute__((always_inline))
 #include "ctu_filter.h"
+#include "ctu_ticket.h"
 #include <vector>
 
 namespace {
@@ -29,6 +30,7 @@ struct filter_args {
   const fpic_dev *pics;
   int32_t *ticket, *sao_done, *final_done;
   int wc, hc, n_pictures, W, H;
+  int row0, row1;               // the CTU rows of this launch (a band of every picture; the whole picture: 0, hc)
   const int32_t *searched;      // BEHIND: [picture][ctu], the search's "done" flags (uvgi_ctu_plan_done_flags)
 };
 
@@ -43,23 +45,18 @@ __global__ void __launch_bounds__(256) ctu_filter_kernel(filter_args A)
   for (;;) {
   if (threadIdx.x == 0) s_ticket = atomicAdd(A.ticket, 1);
   __syncthreads();
-  // ticket -> (diagonal cx + cy, picture, row): every CTU comes after its left and upper neighbour; pictures interleaved
+  // ticket -> (picture, row, column) in the band's wavefront order (ctu_ticket.h): every CTU comes after its left, upper and upper right
+  // neighbour; pictures interleaved
   const int wc = A.wc, hc = A.hc, ctus = wc * hc;
-  if (BEHIND && s_ticket >= ctus * A.n_pictures) break;
-  int t = s_ticket, d = 0;
-  for (;; ++d) {
-    const int lo = d - (wc - 1) > 0 ? d - (wc - 1) : 0, hi = d < hc - 1 ? d : hc - 1, cnt = (hi - lo + 1) * A.n_pictures;
-    if (t < cnt) break;
-    t -= cnt;
-  }
-  const int lo = d - (wc - 1) > 0 ? d - (wc - 1) : 0, hi = d < hc - 1 ? d : hc - 1, per = hi - lo + 1;
-  const int pic = t / per, cy = lo + (t - pic * per), cx = d - cy;
+  if (s_ticket >= wc * (A.row1 - A.row0) * A.n_pictures) break;
+  const uvgi_ticket_ctu T = uvgi_filter_ticket(s_ticket, wc, A.row0, A.row1, A.n_pictures);
+  const int pic = T.pic, cy = T.cy, cx = T.cx;
   const fpic_dev &D = A.pics[pic];
   ctuf::filt_ctu F;
   F.rec_y = D.rec_y; F.rec_u = D.rec_u; F.rec_v = D.rec_v; F.src_y = D.src_y; F.src_u = D.src_u; F.src_v = D.src_v;
   F.rec_stride = D.rec_stride; F.rec_stride_c = D.rec_stride_c; F.src_stride = D.src_stride; F.src_stride_c = D.src_stride_c;
   F.scu = D.scu; F.scu_stride = D.scu_stride;
-  F.W = A.W; F.H = A.H; F.cx = cx; F.cy = cy; F.wc = wc; F.hc = hc;
+  F.W = A.W; F.H = A.H; F.cx = cx; F.cy = cy; F.wc = wc; F.hc = hc; F.row0 = A.row0;
   F.sao_done = A.sao_done + (size_t)pic * ctus; F.final_done = A.final_done + (size_t)pic * ctus;
   if (BEHIND) {
     // the CTU's own flag: its left / upper / upper-left neighbours, whose samples and side information the stage reads too, were searched before it
@@ -145,9 +142,18 @@ const int32_t *uvgi_filter_final_flags(int n_pictures, int pic_w, int pic_h, con
 // flags, the flags zeroed beforehand by uvgi_filter_reset
 int uvgi_filter_run(int bitdepth, int n_pictures, int pic_w, int pic_h, void *workspace, const int32_t *searched, int max_workgroups, void *stream)
 {
+  return uvgi_filter_run_rows(bitdepth, n_pictures, pic_w, pic_h, 0, (pic_h + 63) / 64, workspace, searched, max_workgroups, stream);
+}
+
+// ... over the CTU rows [row0, row1) of every picture.  The kernel KNOWS row0: a CTU of row row0 waits for no flag of row row0 - 1 (the flags
+// of rows outside the band are never set by this launch; what the row reads of the row above is in the buffers before the launch).
+int uvgi_filter_run_rows(int bitdepth, int n_pictures, int pic_w, int pic_h, int row0, int row1, void *workspace, const int32_t *searched, int max_workgroups,
+                         void *stream)
+{
   UVGHIP_REQUIRE_READY();
   UVGHIP_REQUIRE_DEPTH(bitdepth);
-  if (n_pictures <= 0 || pic_w <= 0 || pic_h <= 0 || !workspace || (searched && max_workgroups < 1)) return uvghip_set_error(hipErrorInvalidValue, __func__);
+  if (n_pictures <= 0 || pic_w <= 0 || pic_h <= 0 || !workspace || (searched && max_workgroups < 1) || row0 < 0 || row0 >= row1 || row1 > (pic_h + 63) / 64)
+    return uvghip_set_error(hipErrorInvalidValue, __func__);
   const fl_layout L = layout(n_pictures, pic_w, pic_h);
   unsigned char *ws = static_cast<unsigned char *>(workspace);
   hipStream_t st = uvghip_stream(stream);
@@ -158,8 +164,9 @@ int uvgi_filter_run(int bitdepth, int n_pictures, int pic_w, int pic_h, void *wo
   A.sao_done = reinterpret_cast<int32_t *>(ws + L.sao_done);
   A.final_done = reinterpret_cast<int32_t *>(ws + L.final_done);
   A.wc = (pic_w + 63) / 64; A.hc = (pic_h + 63) / 64; A.n_pictures = n_pictures; A.W = pic_w; A.H = pic_h;
+  A.row0 = row0; A.row1 = row1;
   A.searched = searched;
-  const int total = A.wc * A.hc * n_pictures, grid = searched && max_workgroups < total ? max_workgroups : total;
+  const int total = A.wc * (row1 - row0) * n_pictures, grid = searched && max_workgroups < total ? max_workgroups : total;
   void *args[] = {&A};
   (void)hipLaunchKernel(filter_kernel(bitdepth, searched != nullptr), dim3(grid), dim3(256), args, bitdepth == 8 ? sizeof(ctuf::filt_lds<uint8_t>) : sizeof(ctuf::filt_lds<uint16_t>), st);
   UVGHIP_CHECK_LAUNCH();

@@ -138,6 +138,11 @@ int uvgi_filter_prepare(int bitdepth, const uvghip_ctu_params_t *params, const u
 // (a waiting workgroup holds its slot; the cap keeps the device for the search).
 int uvgi_filter_run(int bitdepth, int n_pictures, int pic_w, int pic_h, void *workspace, const int32_t *searched, int max_workgroups, void *stream);
 int uvgi_filter_reset(int n_pictures, int pic_w, int pic_h, void *workspace, void *stream);
+// ... the same launch over the CTU rows [row0, row1) of every picture (a band of a picture sharded by CTU rows): the band's CTUs only, in
+// wavefront order within the band (ctu_ticket.h).  The kernel knows row0: a CTU of the band's first row waits for no flag of the row above,
+// whose unfiltered samples, side information, deblocked rows, SAO decisions and models the caller has put into the buffers.
+int uvgi_filter_run_rows(int bitdepth, int n_pictures, int pic_w, int pic_h, int row0, int row1, void *workspace, const int32_t *searched, int max_workgroups,
+                         void *stream);
 // ... the stage's own per-CTU "final" flags [picture][ctu] (DEVICE memory): 1 when the CTU's SAO decision and its part of the output picture
 // are published -- what uvgi_encode_slice_rows_behind waits for
 const int32_t *uvgi_filter_final_flags(int n_pictures, int pic_w, int pic_h, const void *workspace);
@@ -164,6 +169,10 @@ const int32_t *uvgi_search_pb_inflight_final_flags(int n_pictures, int pic_w, in
 // table that later runs reuse: uvghip_encode_slice_rows with pictures == NULL); ordered == true in stream order on `st` (callers that take
 // a stream: nothing waits for it).
 int uvgi_slice_rows_prepare(const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, int n_pictures, void *workspace, bool ordered, hipStream_t st);
+// uvghip_encode_slice_rows with the table already prepared, over the CTU rows [row0, row1) of every picture: one wave per row of the band; a
+// row's start models and its SAO models come from the buffers (the first CTU of the row above: of the band above for row0).
+int uvgi_encode_slice_rows_band(int bitdepth, const uvghip_ctu_params_t *params, int n_pictures, const int32_t *sao_info, const uint16_t *sao_models, int row0, int row1,
+                                void *workspace, uint8_t *out, int row_cap, int32_t *row_bytes, void *stream);
 // uvghip_encode_slice_rows with the table already prepared, for pictures whose search is complete but whose in-loop filters (the SAO
 // decisions the slice data carries) are finished by ANOTHER launch beside this one: a row waits for each of its CTUs' final_flags
 // ([picture][ctu]) and for the first CTU of the row above (its SAO models).  The caller orders the flags' zeroing before this call's
@@ -179,6 +188,7 @@ int uvgi_encode_slice_rows_behind(int bitdepth, const uvghip_ctu_params_t *param
 // ---- loop_plan.hip: the all-intra loop plan, for loop_pb.hip (I pictures in the flight: uvghip_loop_pb_run_inflight_intra) -------------
 struct uvghip_loop_plan {
   int bitdepth, n, w, h, sao_type, ctus;
+  int row0 = 0, row1 = 0;                 // the CTU rows the plan runs (uvghip_loop_plan_create_rows; the whole picture: 0, hc)
   uvghip_ctu_plan_t *search;
   std::vector<uvghip_loop_picture_t> pics;
   // carved out of the caller's workspace
@@ -199,6 +209,11 @@ struct uvghip_loop_plan {
   uint8_t *pack_dev = nullptr, *pack_host = nullptr;
   size_t pack_cap = 0;
   unsigned long long *pack_base = nullptr;    // device: [n + 1] byte offsets of the pictures in the packed buffer, then [n] row pitches
+  // a band plan's hand-over (uvghip_loop_plan_halo*): what it receives from the band above [0] / sends to the band below [1], all pictures
+  std::vector<uvghip_halo_piece_t> halo[2];
+  std::vector<size_t> halo_at[2];         // each piece's offset in the packed message
+  size_t halo_bytes = 0;
+  void *halo_dev[2] = {nullptr, nullptr}; // device: the two piece tables of the pack / unpack kernels
 };
 int uvgi_loop_plan_side_streams(uvghip_loop_plan *pl);
 

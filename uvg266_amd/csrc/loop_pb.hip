@@ -258,6 +258,7 @@ extern "C" int uvghip_loop_pb_run_inflight_intra(int bitdepth, uvghip_loop_plan_
     const uvghip_loop_plan *pl = intra_plans[k];
     if (!pl || pl->bitdepth != bitdepth || pl->w != w || pl->h != h || pl->sao_type != sao_type)
       return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run_inflight_intra: a plan's size, bit depth or sao_type differs from the call's");
+    if (pl->row0 > 0 || pl->row1 < pl->hc) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_run_inflight_intra: a band plan (uvghip_loop_plan_create_rows) holds a part of its pictures");
     n_intra += pl->n;
     // the plan's launch beside the flight, whose workgroups take whole CUs: one workgroup per CTU the pictures' wavefronts can have in progress
     // (more only wait and take CUs from the flight), which the flight leaves the CUs for

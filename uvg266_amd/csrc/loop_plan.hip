@@ -43,7 +43,83 @@ extern "C" int uvghip_loop_plan_create(int bitdepth, const uvghip_ctu_params_t *
   UVGHIP_REQUIRE_DEPTH(bitdepth);
   if (!params || !pictures || n_pictures <= 0 || !workspace || !plan_out || sao_type < 1 || sao_type > 3)
     return uvghip_set_error(hipErrorInvalidValue, __func__);
+  return uvghip_loop_plan_create_rows(bitdepth, params, pictures, n_pictures, sao_type, 0, (params->pic_h + 63) / 64, workspace, plan_out);
+}
+
+namespace {
+// The hand-over of a band plan at the boundary above CTU row `b` (side 0: b = row0, the plan receives; side 1: b = row1, it sends): kind
+// after kind, inside a kind picture after picture -- the order of the packed message.  Every extent is what the three launches read of
+// the row above: ctu_filter.h (tile from 64 cy - 16; F from 64 cy - delay with the edge classes' row above it, D from 64 cy - 8;
+// sao_region's decisions of the CTU row the rows lie in; the merge candidates and the models of the chain), slice_coder.hip (one unit row
+// of border, the row's start models, its SAO models), ctu_search.hip (the last line, the last unit row, the models).
+void halo_list(const uvghip_loop_plan *pl, const unsigned char *snap, int b, std::vector<uvghip_halo_piece_t> &out, std::vector<size_t> &at, size_t &total)
+{
+  const size_t bps = pl->bitdepth == 8 ? 1 : 2;
+  const int w = pl->w, wc = (w + 63) / 64, Y = 64 * b;
+  const size_t plane = (size_t)w * pl->h * bps, planes = plane * 3 / 2;
+  total = 0;
+  auto add = [&](void *base, size_t pitch, size_t first_row, int rows, size_t row_bytes) {
+    out.push_back(uvghip_halo_piece_t{static_cast<unsigned char *>(base) + first_row * pitch, row_bytes, pitch, rows, 0});
+    at.push_back(total);
+    total += row_bytes * rows;
+  };
+  const int n = pl->n;
+  for (int i = 0; i < n; ++i) { const uvghip_ctu_picture_t &q = pl->pics[i].search; add(q.rec_y, q.rec_stride * bps, Y - 16, 16, w * bps); }
+  for (int i = 0; i < n; ++i) { const uvghip_ctu_picture_t &q = pl->pics[i].search; add(q.rec_u, q.rec_stride_c * bps, Y / 2 - 8, 8, w / 2 * bps); }
+  for (int i = 0; i < n; ++i) { const uvghip_ctu_picture_t &q = pl->pics[i].search; add(q.rec_v, q.rec_stride_c * bps, Y / 2 - 8, 8, w / 2 * bps); }
+  for (int i = 0; i < n; ++i) { const uvghip_ctu_picture_t &q = pl->pics[i].search; add(q.cu, (size_t)q.cu_stride * sizeof(uvghip_scu_t), Y / 4 - 4, 4, (size_t)wc * 16 * sizeof(uvghip_scu_t)); }
+  if (pl->sao_type) {
+    for (int i = 0; i < n; ++i) add(const_cast<unsigned char *>(snap) + (size_t)i * planes, w * bps, Y - 11, 3, w * bps);
+    for (int i = 0; i < n; ++i) add(const_cast<unsigned char *>(snap) + (size_t)i * planes + plane, w / 2 * bps, Y / 2 - 6, 2, w / 2 * bps);
+    for (int i = 0; i < n; ++i) add(const_cast<unsigned char *>(snap) + (size_t)i * planes + plane + plane / 4, w / 2 * bps, Y / 2 - 6, 2, w / 2 * bps);
+    for (int i = 0; i < n; ++i) add(pl->sao_info + (size_t)i * pl->ctus * 34, (size_t)wc * 34 * 4, b - 1, 1, (size_t)wc * 34 * 4);
+  }
+  const size_t mrow = (size_t)UVGHIP_CTU_MODELS * 4;          // a model set; the third set of CTU k is row 3 k + 2
+  for (int i = 0; i < n; ++i) add(pl->pics[i].search.models, mrow, (size_t)(b - 1) * wc * 3 + 2, 1, mrow);
+  if (pl->sao_type)
+    for (int i = 0; i < n; ++i) add(pl->sao_models + (size_t)i * pl->ctus * 6, 12, (size_t)(b - 1) * wc, 1, 12);
+}
+
+// The pack / unpack kernels: plain copies, one workgroup per (piece, row) -- grid.x the piece, grid.y the row (a piece has at most 16) --
+// between a piece's row and its place in the message.  16 bytes per lane where both addresses allow (planes and the side information of
+// the usual sizes: every lane of a wave in one 1 KB stretch), else 4 bytes, else bytes; the remainder of a row byte by byte.
+struct halo_dev_piece { unsigned char *ptr; unsigned long long pitch, row_bytes, at; int rows, pad; };
+
+template <bool PACK>
+__global__ void __launch_bounds__(256) halo_copy_kernel(const halo_dev_piece *__restrict__ pieces, unsigned char *__restrict__ message)
+{
+  const halo_dev_piece P = pieces[blockIdx.x];
+  const int r = blockIdx.y;
+  if (r >= P.rows) return;
+  unsigned char *plane = P.ptr + (size_t)r * P.pitch, *msg = message + P.at + (size_t)r * P.row_bytes;
+  const unsigned char *src = PACK ? plane : msg;
+  unsigned char *dst = PACK ? msg : plane;
+  const size_t nb = P.row_bytes;
+  const unsigned long long both = (unsigned long long)(uintptr_t)src | (unsigned long long)(uintptr_t)dst;
+  size_t done = 0;
+  if (!(both & 15)) {
+    const size_t nv = nb >> 4;
+    for (size_t i = threadIdx.x; i < nv; i += blockDim.x) reinterpret_cast<uint4 *>(dst)[i] = reinterpret_cast<const uint4 *>(src)[i];
+    done = nv << 4;
+  } else if (!(both & 3)) {
+    const size_t nv = nb >> 2;
+    for (size_t i = threadIdx.x; i < nv; i += blockDim.x) reinterpret_cast<uint32_t *>(dst)[i] = reinterpret_cast<const uint32_t *>(src)[i];
+    done = nv << 2;
+  }
+  for (size_t i = done + threadIdx.x; i < nb; i += blockDim.x) dst[i] = src[i];
+}
+}  // namespace
+
+extern "C" int uvghip_loop_plan_create_rows(int bitdepth, const uvghip_ctu_params_t *params, const uvghip_loop_picture_t *pictures, int n_pictures,
+                                            int sao_type, int ctu_row0, int ctu_row1, void *workspace, uvghip_loop_plan_t **plan_out)
+{
+  UVGHIP_REQUIRE_READY();
+  UVGHIP_REQUIRE_DEPTH(bitdepth);
+  if (!params || !pictures || n_pictures <= 0 || !workspace || !plan_out || sao_type < 0 || sao_type > 3)
+    return uvghip_set_error(hipErrorInvalidValue, __func__);
   const int w = params->pic_w, h = params->pic_h;
+  if (w <= 0 || h <= 0 || ctu_row0 < 0 || ctu_row1 > (h + 63) / 64 || ctu_row0 >= ctu_row1)
+    return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_plan_create_rows: CTU row range");
   // the filters run without a chroma QP table (deblock.hip: identity), so a search that quantises chroma at another QP than luma
   // would be filtered with the wrong tc: refused rather than silently different (the reference's default table is the identity)
   if (params->qp_c != params->qp) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_plan_create: qp_c != qp needs a chroma QP table, which the loop plan does not take");
@@ -57,8 +133,9 @@ extern "C" int uvghip_loop_plan_create(int bitdepth, const uvghip_ctu_params_t *
   uvghip_loop_plan *pl = new (std::nothrow) uvghip_loop_plan;
   if (!pl) return uvghip_set_error(hipErrorOutOfMemory, __func__);
   pl->search = nullptr;
-  if (int rc = uvghip_ctu_plan_create(bitdepth, params, sp.data(), n_pictures, ws + L.search, &pl->search)) { delete pl; return rc; }
+  if (int rc = uvghip_ctu_plan_create_rows(bitdepth, params, sp.data(), n_pictures, ctu_row0, ctu_row1, ws + L.search, &pl->search)) { delete pl; return rc; }
   const int wc = (w + 63) / 64, hc = (h + 63) / 64;
+  pl->row0 = ctu_row0; pl->row1 = ctu_row1;
   pl->bitdepth = bitdepth; pl->n = n_pictures; pl->w = w; pl->h = h; pl->sao_type = sao_type;
   pl->ctus = wc * hc;
   pl->pics.assign(pictures, pictures + n_pictures);
@@ -80,7 +157,69 @@ extern "C" int uvghip_loop_plan_create(int bitdepth, const uvghip_ctu_params_t *
   for (int i = 0; i < n_pictures; ++i)
     fl[i] = uvgi_pb_filter_of(pictures[i], ws + L.snap + (size_t)i * planes, bitdepth, w, h, pl->sao_info + (size_t)i * pl->ctus * 34, pl->sao_models + (size_t)i * pl->ctus * 6, sao_type);
   if (int rc = uvgi_filter_prepare(bitdepth, params, sp.data(), fl.data(), n_pictures, 2, pl->filt_ws)) { uvghip_ctu_plan_destroy(pl->search); delete pl; return rc; }
+  // a band's hand-over: the piece lists, and their tables for the pack / unpack kernels on the device (synchronous, once, as the tables above)
+  for (int side = 0; side < 2; ++side) {
+    if (side == 0 ? ctu_row0 == 0 : ctu_row1 == hc) continue;
+    halo_list(pl, ws + L.snap, side == 0 ? ctu_row0 : ctu_row1, pl->halo[side], pl->halo_at[side], pl->halo_bytes);
+    const size_t np = pl->halo[side].size();
+    std::vector<halo_dev_piece> hd(np);
+    for (size_t i = 0; i < np; ++i) {
+      const uvghip_halo_piece_t &q = pl->halo[side][i];
+      hd[i] = halo_dev_piece{static_cast<unsigned char *>(q.ptr), q.pitch, q.row_bytes, pl->halo_at[side][i], q.rows, 0};
+    }
+    hipError_t e = hipMalloc(&pl->halo_dev[side], np * sizeof(halo_dev_piece));
+    if (e == hipSuccess) e = hipMemcpy(pl->halo_dev[side], hd.data(), np * sizeof(halo_dev_piece), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { uvghip_loop_plan_destroy(pl); return uvghip_set_error(e, __func__); }
+  }
   *plan_out = pl;
+  return 0;
+}
+
+extern "C" int uvghip_loop_plan_halo(const uvghip_loop_plan_t *pl, int side, uvghip_halo_piece_t *pieces, int cap, int *n)
+{
+  if (!pl || !n || cap < 0 || (cap && !pieces)) return uvghip_set_error(hipErrorInvalidValue, __func__);
+  if (side != 0 && side != 1) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_plan_halo: side is 0 (received from the band above) or 1 (sent to the band below)");
+  const std::vector<uvghip_halo_piece_t> &h = pl->halo[side];
+  *n = (int)h.size();
+  if ((size_t)cap < h.size()) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_plan_halo: cap is smaller than the number of pieces (*n)");
+  for (size_t i = 0; i < h.size(); ++i) pieces[i] = h[i];
+  return 0;
+}
+
+extern "C" size_t uvghip_loop_plan_halo_bytes(const uvghip_loop_plan_t *pl) { return pl ? pl->halo_bytes : 0; }
+
+namespace {
+int halo_copy(uvghip_loop_plan *pl, int side, void *message, void *stream, const char *none)
+{
+  if (pl->halo[side].empty()) return uvghip_set_error(hipErrorInvalidValue, none);
+  const dim3 grid((unsigned)pl->halo[side].size(), 16);
+  const halo_dev_piece *tab = static_cast<const halo_dev_piece *>(pl->halo_dev[side]);
+  if (side) hipLaunchKernelGGL(halo_copy_kernel<true>, grid, dim3(256), 0, uvghip_stream(stream), tab, static_cast<unsigned char *>(message));
+  else hipLaunchKernelGGL(halo_copy_kernel<false>, grid, dim3(256), 0, uvghip_stream(stream), tab, static_cast<unsigned char *>(message));
+  UVGHIP_CHECK_LAUNCH();
+}
+}  // namespace
+
+extern "C" int uvghip_loop_plan_halo_pack(uvghip_loop_plan_t *pl, void *message, void *stream)
+{
+  UVGHIP_REQUIRE_READY();
+  if (!pl || !message) return uvghip_set_error(hipErrorInvalidValue, __func__);
+  return halo_copy(pl, 1, message, stream, "uvghip_loop_plan_halo_pack: the plan holds the picture's last CTU row: nothing goes down");
+}
+
+extern "C" int uvghip_loop_plan_halo_unpack(uvghip_loop_plan_t *pl, const void *message, void *stream)
+{
+  UVGHIP_REQUIRE_READY();
+  if (!pl || !message) return uvghip_set_error(hipErrorInvalidValue, __func__);
+  return halo_copy(pl, 0, const_cast<void *>(message), stream, "uvghip_loop_plan_halo_unpack: the plan holds the picture's first CTU row: nothing comes from above");
+}
+
+extern "C" int uvghip_loop_plan_out_rows(const uvghip_loop_plan_t *pl, int *y0, int *y1)
+{
+  if (!pl || !y0 || !y1) return uvghip_set_error(hipErrorInvalidValue, __func__);
+  const int delay = pl->sao_type ? 10 : 8;
+  *y0 = pl->row0 ? 64 * pl->row0 - delay : 0;
+  *y1 = pl->row1 == pl->hc ? pl->h : 64 * pl->row1 - delay;
   return 0;
 }
 
@@ -110,7 +249,7 @@ extern "C" int uvghip_loop_plan_run_overlapped(uvghip_loop_plan_t *pl, void *str
   if (!pl) return uvghip_set_error(hipErrorInvalidValue, __func__);
   // only while the pictures' wavefronts leave half the device free, and what runs beside the search capped (internal.h: the measurements)
   const int wc = (pl->w + 63) / 64, per = wc < pl->hc ? wc : pl->hc;
-  if ((long long)pl->n * per > uvgi_overlap_max_ctus) return uvghip_loop_plan_run(pl, stream);
+  if ((long long)pl->n * per > uvgi_overlap_max_ctus || pl->row0 > 0 || pl->row1 < pl->hc) return uvghip_loop_plan_run(pl, stream);          // (no side-stream schedule for bands)
   hipStream_t st = uvghip_stream(stream);
   if (int rc = uvgi_loop_plan_side_streams(pl)) return rc;
   // all flags to zero in `stream`, the side streams behind that; then the search, so that it is in the queue before anything waits for it
@@ -147,7 +286,7 @@ extern "C" int uvghip_loop_plan_run_filters(uvghip_loop_plan_t *pl, void *stream
 {
   UVGHIP_REQUIRE_READY();
   if (!pl) return uvghip_set_error(hipErrorInvalidValue, __func__);
-  if (int rc = uvgi_filter_run(pl->bitdepth, pl->n, pl->w, pl->h, pl->filt_ws, nullptr, 0, stream)) return rc;
+  if (int rc = uvgi_filter_run_rows(pl->bitdepth, pl->n, pl->w, pl->h, pl->row0, pl->row1, pl->filt_ws, nullptr, 0, stream)) return rc;
   return uvghip_loop_plan_run_coder(pl, stream);
 }
 
@@ -156,7 +295,8 @@ extern "C" int uvghip_loop_plan_run_coder(uvghip_loop_plan_t *pl, void *stream)
 {
   UVGHIP_REQUIRE_READY();
   if (!pl) return uvghip_set_error(hipErrorInvalidValue, __func__);
-  return uvghip_encode_slice_rows(pl->bitdepth, &pl->ctu_params, nullptr, pl->n, pl->sao_info, pl->sao_models, pl->coder_ws, pl->rows, pl->row_cap, pl->row_bytes, stream);
+  return uvgi_encode_slice_rows_band(pl->bitdepth, &pl->ctu_params, pl->n, pl->sao_type ? pl->sao_info : nullptr, pl->sao_type ? pl->sao_models : nullptr, pl->row0, pl->row1,
+                                     pl->coder_ws, pl->rows, pl->row_cap, pl->row_bytes, stream);
 }
 
 extern "C" int uvghip_loop_plan_slice_data(const uvghip_loop_plan_t *pl, const uint8_t **rows, const int32_t **row_bytes, int *row_cap, int *n_rows)
@@ -175,6 +315,7 @@ extern "C" int uvghip_loop_plan_picture_nals(uvghip_loop_plan_t *pl, int picture
 {
   UVGHIP_REQUIRE_READY();
   if (!pl || picture < 0 || picture >= pl->n || poc < 0 || !len || (!out && cap)) return uvghip_set_error(hipErrorInvalidValue, __func__);
+  if (pl->row0 > 0 || pl->row1 < pl->hc) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_plan_picture_nals: a band plan holds a part of the picture (gather the bands' rows and checksum terms)");
   hipStream_t st = uvghip_stream(stream);
   const uvghip_loop_picture_t &q = pl->pics[picture];
   uint32_t *d_sums = pl->sums + 3 * (size_t)picture;
@@ -193,7 +334,7 @@ extern "C" int uvghip_loop_plan_picture_nals(uvghip_loop_plan_t *pl, int picture
   for (int r = 0; r < pl->hc; ++r)
     UVGHIP_TRY(hipMemcpyAsync(rows.data() + (size_t)r * pitch, pl->rows + ((size_t)picture * pl->hc + r) * pl->row_cap, (size_t)nb[r], hipMemcpyDeviceToHost, st));
   UVGHIP_TRY(hipStreamSynchronize(st));
-  return uvghip_write_picture_nals(poc, 1, rows.data(), pitch, nb.data(), pl->hc, sums, out, cap, len);
+  return uvghip_write_picture_nals(poc, pl->sao_type != 0, rows.data(), pitch, nb.data(), pl->hc, sums, out, cap, len);
 }
 
 // The NAL units of ALL pictures of the group after a run, as pictures first_poc, first_poc + 1, ... : what n calls of
@@ -231,6 +372,7 @@ extern "C" int uvghip_loop_plan_group_nals(uvghip_loop_plan_t *pl, int first_poc
 {
   UVGHIP_REQUIRE_READY();
   if (!pl || first_poc < 0 || !lens || (!out && cap)) return uvghip_set_error(hipErrorInvalidValue, __func__);
+  if (pl->row0 > 0 || pl->row1 < pl->hc) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_plan_group_nals: a band plan holds a part of the picture (gather the bands' rows and checksum terms)");
   if (pl->row_cap & 15) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_plan_group_nals: the plan's row slots are not 16-byte multiples");
   hipStream_t st = uvghip_stream(stream);
   const int n = pl->n, hc = pl->hc;
@@ -275,7 +417,7 @@ extern "C" int uvghip_loop_plan_group_nals(uvghip_loop_plan_t *pl, int first_poc
   size_t used = 0;
   for (int p = 0; p < n; ++p) {
     size_t len = 0;
-    if (int rc = uvghip_write_picture_nals(first_poc + p, 1, pl->pack_host + base[p], pitch[p], nb.data() + (size_t)p * hc, hc, sums.data() + 3 * (size_t)p,
+    if (int rc = uvghip_write_picture_nals(first_poc + p, pl->sao_type != 0, pl->pack_host + base[p], pitch[p], nb.data() + (size_t)p * hc, hc, sums.data() + 3 * (size_t)p,
                                            out ? out + used : nullptr, cap > used ? cap - used : 0, &len)) return rc;
     lens[p] = len;
     used += len;
@@ -371,6 +513,7 @@ extern "C" void uvghip_loop_plan_destroy(uvghip_loop_plan_t *pl)
   if (pl->pack_host) (void)hipHostFree(pl->pack_host);
   if (pl->pack_base) (void)hipFree(pl->pack_base);
   for (int i = 0; i < 2; ++i) {
+    if (pl->halo_dev[i]) (void)hipFree(pl->halo_dev[i]);
     if (pl->side[i]) (void)hipStreamDestroy(pl->side[i]);
     if (pl->ev_side[i]) (void)hipEventDestroy(pl->ev_side[i]);
   }

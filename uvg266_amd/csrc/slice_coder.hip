@@ -581,7 +581,7 @@ template <bool PERSIST = false>
 __global__ void __launch_bounds__(64)
 slice_rows_kernel(const pic_dev *__restrict__ pics, const pb_dev *__restrict__ pbs, const int32_t *__restrict__ sao, const uint16_t *__restrict__ sao_models,
                   int W, int H, int qp, int bitdepth, uint8_t *__restrict__ out, int row_cap, int32_t *__restrict__ row_bytes, const alf_dev *__restrict__ alfs = nullptr,
-                  const int32_t *wait_flags = nullptr, int32_t *ticket = nullptr, int n_pictures = 0)
+                  const int32_t *wait_flags = nullptr, int32_t *ticket = nullptr, int n_pictures = 0, int row0 = 0, int n_rows = 0)
 {
   __shared__ row_state Rs;
   __shared__ int s_job;
@@ -597,7 +597,10 @@ slice_rows_kernel(const pic_dev *__restrict__ pics, const pb_dev *__restrict__ p
     job = s_job;
     if (job >= n_pictures * hc) break;
   }
-  const int pic = PERSIST ? job % n_pictures : job / hc, cy = PERSIST ? job / n_pictures : job - pic * hc;
+  // (not PERSIST) n_rows > 0: the launch is a wave per row of the band [row0, row0 + n_rows) of every picture; the row above the band is complete
+  // in the buffers (its side information, the models behind its first CTU, its SAO decisions and models)
+  const int per = !PERSIST && n_rows > 0 ? n_rows : hc;
+  const int pic = PERSIST ? job % n_pictures : job / per, cy = PERSIST ? job / n_pictures : row0 + (job - pic * per);
   const pic_dev D = pics[pic];
   const pb_dev *PB = pbs ? &pbs[pic] : nullptr;
   const int slice = PB ? PB->slice_type : 2, init_qp = PB ? PB->frame_qp : qp;
@@ -923,6 +926,21 @@ extern "C" int uvghip_encode_slice_rows(int bitdepth, const uvghip_ctu_params_t 
     if (int rc = uvgi_slice_rows_prepare(params, pictures, n_pictures, workspace, false, st)) return rc;
   slice_rows_kernel<false><<<n_pictures * hc, 64, 0, st>>>(static_cast<const pic_dev *>(workspace), nullptr, sao_info, sao_models, W, H, params->qp, bitdepth, out,
                                                     row_cap, row_bytes);
+  UVGHIP_CHECK_LAUNCH();
+}
+
+// uvghip_encode_slice_rows with the table already prepared, over the CTU rows [row0, row1) of every picture: a wave per row of the band.  Rows
+// outside the band are not written (bytes and lengths).  sao_info == NULL: no SAO syntax.
+int uvgi_encode_slice_rows_band(int bitdepth, const uvghip_ctu_params_t *params, int n_pictures, const int32_t *sao_info, const uint16_t *sao_models, int row0, int row1,
+                                void *workspace, uint8_t *out, int row_cap, int32_t *row_bytes, void *stream)
+{
+  UVGHIP_REQUIRE_READY();
+  UVGHIP_REQUIRE_DEPTH(bitdepth);
+  if (!params || n_pictures <= 0 || !workspace || !out || row_cap <= 0 || !row_bytes || (sao_info && !sao_models)) return uvghip_set_error(hipErrorInvalidValue, __func__);
+  const int W = params->pic_w, H = params->pic_h, hc = (H + 63) / 64;
+  if (W <= 0 || H <= 0 || (W & 7) || (H & 7) || params->qp < 0 || params->qp > 63 || row0 < 0 || row0 >= row1 || row1 > hc) return uvghip_set_error(hipErrorInvalidValue, __func__);
+  slice_rows_kernel<false><<<n_pictures * (row1 - row0), 64, 0, uvghip_stream(stream)>>>(static_cast<const pic_dev *>(workspace), nullptr, sao_info, sao_models, W, H, params->qp,
+                                                                                         bitdepth, out, row_cap, row_bytes, nullptr, nullptr, nullptr, 0, row0, row1 - row0);
   UVGHIP_CHECK_LAUNCH();
 }
 

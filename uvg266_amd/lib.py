@@ -143,6 +143,11 @@ class LoopPicture(ctypes.Structure):
                 ("out_stride", ctypes.c_int32), ("out_stride_c", ctypes.c_int32)]
 
 
+class HaloPiece(ctypes.Structure):
+    """uvghip_halo_piece_t."""
+    _fields_ = [("ptr", ctypes.c_void_p), ("row_bytes", ctypes.c_size_t), ("pitch", ctypes.c_size_t), ("rows", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class AlfDecision(ctypes.Structure):
     """uvghip_alf_decision_t: what the host's ALF derivation returns for one picture (host arrays)."""
     _fields_ = [("alf_type", ctypes.c_int32), ("enabled", ctypes.c_int32 * 3), ("n_luma_aps", ctypes.c_int32), ("luma_aps", ctypes.c_void_p), ("chroma_aps", ctypes.c_void_p),
@@ -254,6 +259,12 @@ SIGNATURES = {
     "uvghip_ctu_plan_destroy": (None, [c_vp]),
     "uvghip_slice_rows_workspace_bytes": (ctypes.c_size_t, [c_int]),
     "uvghip_loop_plan_slice_data": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "uvghip_loop_plan_create_rows": (c_int, [c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "uvghip_loop_plan_halo": (c_int, [c_vp, c_int, c_vp, c_int, c_vp]),
+    "uvghip_loop_plan_halo_bytes": (ctypes.c_size_t, [c_vp]),
+    "uvghip_loop_plan_halo_pack": (c_int, [c_vp, c_vp, c_vp]),
+    "uvghip_loop_plan_halo_unpack": (c_int, [c_vp, c_vp, c_vp]),
+    "uvghip_loop_plan_out_rows": (c_int, [c_vp, c_vp, c_vp]),
     "uvghip_encode_slice_rows": (c_int, [c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
     "uvghip_loop_plan_picture_nals": (c_int, [c_vp, c_int, c_int, c_vp, ctypes.c_size_t, c_vp, c_vp]),
     "uvghip_loop_plan_group_nals": (c_int, [c_vp, c_int, c_vp, ctypes.c_size_t, c_vp, c_vp]),
