@@ -2223,15 +2223,21 @@ CTU_DEV int rec_spend(uint32_t rec) { const uint32_t a = rec & 0xffffu; return (
 // Coefficient bit cost by the first wave (same bins, same model adaptation as coeff_bits_serial).  What is sequential in the
 // reference's coder is only the adaptation of each context model along ITS OWN bins, and the bit count is a sum of exact
 // multiples of 2^-15 (order-free).  So: every position's contexts / Rice parameters / bin values are derived by all lanes from the
-// levels (they depend on nothing else), the point where the regular-bin budget runs out is found from per-group totals, and then
-// each lane owns ONE model and walks the positions in coding order, adapting its model at the bins that use it -- two sweeps
-// (sig / gt1 / parity, then gt2) cover the <= 75 models of a block.  Lane 0 codes the last-position prefix and the group flags.
+// levels (they depend on nothing else) and kept as a record per position; whether the regular-bin budget can run out at all is told
+// by seven ballots over the coded groups' totals, and only then lane 0 walks to the point where it does.  Every model then lives in
+// a lane's registers as a packed state:
+// * the sweep: sig / greater-1 / parity (chroma: / greater-2) a lane each, luma's greater-2 models a second one in the lanes 0..20.
+//   The sixteen lanes that hold a group's records pack a position's four (context << 1 | bin) bytes into a key word; the sixteen
+//   steps of a group are unrolled on v_readlane at fixed lanes, each a byte compare and a packed state update (cb_step), with the
+//   next coded group's records in flight meanwhile;
+// * the last-position prefix: a model a lane (0..7: x, 8..15: y), at most four bins each; the two group-flag contexts: the lanes 16
+//   and 17, stepped through the groups from ballots.
+// A bin's cost is the entropy table's entry of the state BEFORE the step (cb_idx); a state does not depend on a cost, so the lookup
+// goes out in the step and is added a step later -- no step waits for LDS.  Only models that coded a bin are written back, and with
+// update == 0 (the 64x64 candidate's blocks) none: nothing is copied.  The bypass-coded bits come from the records.
 // All 64 lanes of wave 0 call it; the returned value is the same on every lane.  Host emulation: the serial walk.
-// BITS = false: the models' adaptation only (the coder's pass: nobody reads the count; returns 0).  No Rice parameters, no entropy-table
-// lookups, no bypass pass, no sums: the sweep's sixteen steps per group are unrolled on v_readlane at fixed lanes, each a compare and
-// a packed state update in registers (cb_step), and the last-position prefix and the group flags -- lane 0's chain of LDS
-// read-modify-writes in the counting variant -- are models in lanes' registers as well (the prefix's: a lane each, at most four
-// bins; the two group-flag contexts: two lanes, stepped through the groups from ballots).
+// BITS = false: the models' adaptation only (the coder's pass: nobody reads the count; returns 0): the same steps without the Rice
+// parameters, the entropy-table lookups, the bypass pass and the sums.
 #if defined(__HIPCC__)
 typedef unsigned short cb_u16x2 __attribute__((ext_vector_type(2)));
 // CTX_UPDATE (m_update) on the packed state: both halves shifted by their own window (v_pk_lshrrev_b16); no borrow or carry crosses
@@ -2242,6 +2248,8 @@ CTU_DEV uint32_t cb_step(uint32_t st, uint32_t rpk, uint32_t gate, uint32_t add)
   const cb_u16x2 sh = __builtin_bit_cast(cb_u16x2, st) >> __builtin_bit_cast(cb_u16x2, rpk);
   return st - (__builtin_bit_cast(uint32_t, sh) & gate) + add;
 }
+// the entropy table's entry of a bin coded with the packed state: (s0 + s1) >> 8 is the model's 8-bit state (m_state)
+CTU_DEV uint32_t cb_idx(uint32_t st, bool one) { return ((((st & 0xffffu) + (st >> 16)) >> 8) << 1) ^ (one ? 1u : 0u); }
 CTU_DEV uint32_t cb_rpk(int rw) { return (uint32_t)(rw >> 4) | (uint32_t)(rw & 15) << 16; }
 CTU_DEV uint32_t cb_addpk(int rw) { return ((0x7fffu >> (rw >> 4)) & 0x7fe0u) | ((0x7fffu >> (rw & 15)) & 0x7ffeu) << 16; }
 #endif
@@ -2306,8 +2314,8 @@ template <typename PX, bool BITS = true> CTU_NOINLINE CTU_DEV double coeff_bits(
   }
   CTU_SYNC();
   // ---- where the regular-bin budget runs out (lane 0; whole groups while they fit) ----
-  bool walk = true;
-  if constexpr (!BITS) {
+  bool walk;
+  {
     // every coded group passes whole while the coded groups' bins together leave 4 of the budget: then the walk below ends with -1
     int mine = 0;
     if (lane <= cg_last) { const int f = scan[lane * 16]; if (cgf[((f >> l2) >> 2) * cgw + ((f & (n - 1)) >> 2)] || lane == 0) mine = gtot[lane] & 0xffff; }
@@ -2337,8 +2345,13 @@ template <typename PX, bool BITS = true> CTU_NOINLINE CTU_DEV double coeff_bits(
   }
   const int sw = walk ? V->rq_i[8] : -1;          // scan positions <= sw are bypass-coded
   RQ_T(29);
-  if constexpr (!BITS) {
-    // ---- the models only ----
+  unsigned long long coded;           // bit g: group g (scan order) is coded
+  uint32_t acc = 0;                   // BITS: the costs of the bins this lane's models code, in units of 2^-15
+  int ibits = 0;                      // BITS: bypass-coded bits
+  {
+    // ---- the models, in lanes' registers ----
+    CTU_LDS const uint32_t *const ebits = LDSP(const uint32_t, tab_ebits());
+    (void)ebits;
     const int last_u = __builtin_amdgcn_readfirstlane(last), sw_u = __builtin_amdgcn_readfirstlane(sw), cgl = last_u >> 4, l15 = lane & 15;
     CTU_LDS const uint8_t *const rate = LDSP(const uint8_t, kRate);
     const uint32_t kGate = 0x7ffe7fe0u;
@@ -2354,7 +2367,8 @@ template <typename PX, bool BITS = true> CTU_NOINLINE CTU_DEV double coeff_bits(
         if (cy + 1 < cgw) ctx |= cgf[cb + cgw] != 0;
       }
       const int gmin = (sw_u + 1) >> 4;                        // groups below it lie behind the budget's end
-      todo = __ballot(on) & (gmin < 64 ? ~0ull << gmin : 0ull);
+      coded = __ballot(on);
+      todo = coded & (gmin < 64 ? ~0ull << gmin : 0ull);
       flg_ctx = __ballot(ctx);
       flg_bin = __ballot(bin);
     }
@@ -2371,6 +2385,11 @@ template <typename PX, bool BITS = true> CTU_NOINLINE CTU_DEV double coeff_bits(
     // a position's key per role, a byte each (sig, greater-1, parity, greater-2): context << 1 | bin, 0xff where it codes no such
     // bin; a lane's model codes the bin where the byte of its role is 2 k or 2 k + 1
     const uint32_t sh8 = role < 0 ? 0u : (uint32_t)role * 8u, k2 = role < 0 ? 0x1000u : (uint32_t)k << 1, l2k = two ? (uint32_t)lane << 1 : 0x1000u;
+    // BITS: a bin costs ebits[] of its model's state BEFORE the step.  The lookup goes out in the step and its result is added in
+    // the next step that runs (pc, gated by ph: the lane's model coded the bin), so no step waits for LDS: the state does not
+    // depend on the cost, and the sum is order-free
+    uint32_t pc = 0, pc2 = 0;
+    bool ph = false, ph2 = false;
     {
       int g = 63 - __builtin_clzll(todo);                      // (the last position's group is coded and in front of the budget's end)
       uint32_t nxt = recs[g * 16 + l15];
@@ -2389,15 +2408,18 @@ template <typename PX, bool BITS = true> CTU_NOINLINE CTU_DEV double coeff_bits(
           const uint32_t kj = (uint32_t)__builtin_amdgcn_readlane((int)keys, j);
           if (kj == 0xffffffffu) continue;                     // (wave-uniform)
           const uint32_t d = ((kj >> sh8) & 0xffu) - k2;
+          if constexpr (BITS) { acc += ph ? pc : 0u; pc = ebits[cb_idx(st, d == 1u)]; ph = d < 2u; }
           st = cb_step(st, rpk, d < 2u ? kGate : 0u, d == 1u ? addpk : 0u);
           if (luma && (kj >> 24) != 0xffu) {                   // (wave-uniform: the position codes a greater-2 bin)
             const uint32_t d2 = (kj >> 24) - l2k;
+            if constexpr (BITS) { acc += ph2 ? pc2 : 0u; pc2 = ebits[cb_idx(st2, d2 == 1u)]; ph2 = d2 < 2u; }
             st2 = cb_step(st2, rpk2, d2 < 2u ? kGate : 0u, d2 == 1u ? addpk2 : 0u);
           }
         }
         if (!more) break;
       }
     }
+    if constexpr (BITS) acc += (ph ? pc : 0u) + (ph2 ? pc2 : 0u);
     if (role >= 0 && update) m[model] = st;
     if (two && update) m[model2] = st2;
     RQ_T(30);
@@ -2414,113 +2436,49 @@ template <typename PX, bool BITS = true> CTU_NOINLINE CTU_DEV double coeff_bits(
       const int arw = rate[amodel];
       const uint32_t arpk = cb_rpk(arw), aaddpk = cb_addpk(arw);
       bool dirty = false;
+      uint32_t ac[4];                                // BITS: the prefix bins' costs, the four lookups in flight together
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int kk = (q << sh) + i;
         const bool in = lane < 16 && i < (1 << sh), one = in && kk < gp, zero = in && kk == gp && gp < gmax;
+        if constexpr (BITS) ac[i] = one || zero ? cb_idx(ast, one) : ~0u;
         ast = cb_step(ast, arpk, one || zero ? kGate : 0u, one ? aaddpk : 0u);
         dirty |= one || zero;
       }
+      if constexpr (BITS) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { const uint32_t c = ebits[ac[i] & 511u]; acc += ac[i] != ~0u ? c : 0u; }
+        if ((lane == 0 || lane == 8) && gp > 3) ibits += (gp - 2) / 2;          // the prefix's bypass bits of x and of y
+      }
       unsigned long long rem = cgl >= 2 ? ((1ull << cgl) - 1) & ~1ull : 0ull;          // the groups cgl - 1 .. 1 code a flag
       const int my = lane - 16;
+      uint32_t fc = 0;                               // BITS: the previous flag's cost, added a step later as in the sweep
+      bool fh = false;
       while (rem) {
         const int g = 63 - __builtin_clzll(rem);
         rem &= ~(1ull << g);
         const int c = (int)((flg_ctx >> g) & 1), b = (int)((flg_bin >> g) & 1);
         const bool hit = my == c;
+        if constexpr (BITS) { acc += fh ? fc : 0u; fc = ebits[cb_idx(ast, b != 0)]; fh = hit; }
         ast = cb_step(ast, arpk, hit ? kGate : 0u, hit && b ? aaddpk : 0u);
         dirty |= hit;
       }
-      if (dirty && update) m[amodel] = ast;          // (only a model that coded a bin: the others may be another wave's)
+      if constexpr (BITS) acc += fh ? fc : 0u;
+      // (only a model that coded a bin: the others may be another wave's.  update == 0 -- the 64x64 candidate's blocks -- counts on the
+      // registers and writes nothing back: no copy of the models is made)
+      if (dirty && update) m[amodel] = ast;
     }
-    CTU_SYNC();
-    RQ_T(31);
-    return 0.0;
-  }
-  // ---- the models, one per lane, along the positions in coding order ----
-  // A group's 16 records are fetched by lanes 0..15 at once and handed out with v_readlane: no memory in the adaptation chain.
-  // 4x4 luma blocks use 16 of the 21 greater-1 / parity / greater-2 models (the diagonal classes of larger blocks never occur) and
-  // chroma has 8 + 3 * 11 models: one sweep covers them; other luma blocks take two (sig / gt1 / parity, then gt2).
-  unsigned long long q15 = 0;         // sum of bit costs in units of 2^-15
-  unsigned long long grp_mask = 0;    // bit g: group g (scan order) is coded
-  for (int g0 = 0; g0 <= cg_last; g0 += 64) {
-    const int g = g0 + lane;
-    int on = 0;
-    if (g <= cg_last) { const int f = scan[g * 16]; on = cgf[((f >> l2) >> 2) * cgw + ((f & (n - 1)) >> 2)] || g == 0; }
-    grp_mask = __ballot(on);            // (ncg <= 64)
-  }
-  const int compact = !t && n == 4;     // 4x4 luma: set offsets 0, 6..20 -> k 0, 1..15
-  const int nk0 = t ? 8 : 12, nks = t ? 11 : (compact ? 16 : 21);
-  // 8 + 3 * 11 chroma / 12 + 3 * 16 compact-luma models fit the 64 lanes; other luma blocks have 12 + 3 * 21 = 75: there the lanes 0..20
-  // own a SECOND model (greater-2, set k = lane) beside their first -- one walk over the positions serves both (the two lookups of a
-  // step are in flight together; two walks cost twice the steps)
-  const bool dual = nk0 + 3 * nks > 64;
-  {
-    int role = -1, k = 0;
-    if (!dual) {
-      if (lane < nk0) { role = 0; k = lane; }
-      else if (lane < nk0 + 3 * nks) { role = 1 + (lane - nk0) / nks; k = (lane - nk0) % nks; }
-      if (compact && role > 0 && k > 0) k += 5;
-    } else { if (lane < 12) { role = 0; k = lane; } else if (lane < 33) { role = 1; k = lane - 12; } else if (lane < 54) { role = 2; k = lane - 33; } }
-    const bool two = dual && lane < 21;
-    const int model = role < 0 ? 0 : (role == 0 ? M_SIG + 12 * t : role == 1 ? M_GT1 + 21 * t : role == 2 ? M_PAR + 21 * t : M_GT2 + 21 * t) + k;
-    const int model2 = M_GT2 + 21 * t + (two ? lane : 0);
-    uint32_t st = m[model], st2 = m[model2];
-    const int r0 = kRate[model] >> 4, r1 = kRate[model] & 15, q0 = kRate[model2] >> 4, q1 = kRate[model2] & 15;
-    const uint32_t add0 = (0x7fffu >> r0) & 0x7fe0u, add1 = (0x7fffu >> r1) & 0x7ffeu, bdd0 = (0x7fffu >> q0) & 0x7fe0u, bdd1 = (0x7fffu >> q1) & 0x7ffeu;
-    // what a record must show for this lane's model to code a bin: field (sig: bits 16..19, others: 20..24) == k, and the gate
-    const uint32_t fsh = role == 0 ? 16 : 20, fmask = role == 0 ? 15u : 31u, rsel = role < 0 ? 31u : (uint32_t)role;
-    CTU_LDS const uint32_t *const ebits = LDSP(const uint32_t, tab_ebits());
-    uint32_t acc = 0;
-    for (int g = cg_last; g >= 0 && g * 16 + 15 > sw; --g) {
-      if (!((grp_mask >> g) & 1)) continue;
-      const uint32_t myrec = recs[g * 16 + (lane & 15)];
-#pragma nounroll
-      for (int j = 15; j >= 0; --j) {
-        const int sp = g * 16 + j;
-        if (sp > last || sp <= sw) continue;
-        const uint32_t rj = (uint32_t)__builtin_amdgcn_readlane((int)myrec, j);
-        const uint32_t aj = rj & 0xffffu;
-        // per role (sig, gt1, parity, gt2): does the position code a bin with one of the role's models, and which -- branch-free
-        const uint32_t gates = ((rj >> 29) & 1u) | (aj != 0 ? 2u : 0u) | (aj > 1 ? 12u : 0u);
-        if (gates == 0) continue;
-        const uint32_t bins = (aj != 0 ? 1u : 0u) | (aj > 1 ? 2u : 0u) | ((aj & 1u) << 2) | (aj >= 4 ? 8u : 0u);
-        const bool hit = ((gates >> rsel) & 1u) && ((rj >> fsh) & fmask) == (uint32_t)k;
-        const uint32_t bin = (bins >> rsel) & 1u;
-        uint32_t s0 = st & 0xffffu, s1 = st >> 16;
-        const uint32_t cost = ebits[(((s0 + s1) >> 8) << 1) ^ bin];
-        s0 -= (s0 >> r0) & 0x7fe0u;
-        s1 -= (s1 >> r1) & 0x7ffeu;
-        s0 += bin ? add0 : 0u;
-        s1 += bin ? add1 : 0u;
-        st = hit ? ((s0 & 0xffffu) | (s1 << 16)) : st;
-        acc += hit ? cost : 0u;
-        if (dual && (gates & 8u)) {                 // (wave-uniform: the position codes a greater-2 bin)
-          const bool hit2 = two && ((rj >> 20) & 31u) == (uint32_t)lane;
-          const uint32_t bin2 = (bins >> 3) & 1u;
-          uint32_t t0 = st2 & 0xffffu, t1 = st2 >> 16;
-          const uint32_t cost2 = ebits[(((t0 + t1) >> 8) << 1) ^ bin2];
-          t0 -= (t0 >> q0) & 0x7fe0u;
-          t1 -= (t1 >> q1) & 0x7ffeu;
-          t0 += bin2 ? bdd0 : 0u;
-          t1 += bin2 ? bdd1 : 0u;
-          st2 = hit2 ? ((t0 & 0xffffu) | (t1 << 16)) : st2;
-          acc += hit2 ? cost2 : 0u;
-        }
-      }
+    if constexpr (!BITS) {
+      CTU_SYNC();
+      RQ_T(31);
+      return 0.0;
     }
-    if (role >= 0 && update) m[model] = st;
-    if (two && update) m[model2] = st2;
-    q15 += acc;
   }
-  RQ_T(30);
-  // ---- bypass-coded parts: remainders, bypass positions, signs ----
-  int ibits = 0;
+  // ---- bypass-coded parts: remainders, bypass positions, signs (the level and the Rice parameters are in the position's record) ----
   for (int sp = lane; sp <= last; sp += 64) {
-    const int g = sp >> 4, f = scan[g * 16];
-    if (!(cgf[((f >> l2) >> 2) * cgw + ((f & (n - 1)) >> 2)] || g == 0)) continue;
+    if (!((coded >> (sp >> 4)) & 1)) continue;
     const uint32_t rec = recs[sp];
-    const unsigned a = (unsigned)iabs_((int)coeff[scan[sp]]);
+    const unsigned a = rec & 0xffffu;
     if (sp > sw) { if (a >= 4) ibits += coeff_remain_bits((a - 4) >> 1, (rec >> 25) & 3, 5); }
     else {
       const unsigned rice = (rec >> 27) & 3, pos0 = 1u << rice;
@@ -2528,53 +2486,7 @@ template <typename PX, bool BITS = true> CTU_NOINLINE CTU_DEV double coeff_bits(
     }
     ibits += a != 0;
   }
-  // ---- lane 0: last-position prefix and the group flags (their models are nobody else's) ----
-  if (lane == 0) {
-    double bits = 0;
-    CTU_LDS uint32_t *mk = m, *mg = m;        // the models of the last position / of the group flags
-    if (!update) {
-      // counting only: these bins still adapt their models WITHIN the block (the reference counts on a copy) -- work on a copy
-      // of the few models involved
-#if defined(CTU_PB)
-      mk = (CTU_LDS uint32_t *)(CTU_WAVE == 0 ? S->pb.cnt_models : (CTU_WAVE == 1 ? S->pb.work0 : pbq(S).cnt_models));       // (every work[] set is some depth's here; the leaf wave: see coeff_bits)
-      mg = mk;
-      for (int i = 0; i < 4; ++i) mk[M_SIGGRP + i] = m[M_SIGGRP + i];
-      for (int i = M_LASTX; i < M_CBF_LUMA; ++i) mk[i] = m[i];
-#else
-      // (the 64x64 candidate, counted beside the walk by two waves at a time while every work[] set is some depth's: the 84 models live in
-      // the wave's reference rows -- a block is counted after its reconstruction -- behind the 4 group-flag models)
-      mk = (CTU_LDS uint32_t *)V->top - (M_LASTX - 4);
-      mg = (CTU_LDS uint32_t *)V->top;
-      for (int i = 0; i < 4; ++i) mg[M_SIGGRP + i] = m[M_SIGGRP + i];
-      for (int i = M_LASTX; i < M_CBF_LUMA; ++i) mk[i] = m[i];
-#endif
-    }
-    const int pos_last = scan[last];
-    const int last_y = pos_last >> l2, last_x = pos_last - (last_y << l2);
-    const int prefix_ctx[8] = {0, 0, 0, 3, 6, 10, 15, 21};
-    const int off = t ? 0 : prefix_ctx[l2];
-    const int sh = t ? clampi(n >> 3, 0, 2) : ((l2 + 1) >> 2);
-    const int bx = M_LASTX + 20 * t + off, by = M_LASTY + 20 * t + off;
-    const int gx = group_idx(last_x), gy = group_idx(last_y), gmax = group_idx(n - 1);
-    int k = 0;
-    for (; k < gx; k++) m_code(mk, 1, bx + (k >> sh), 1, bits);
-    if (gx < gmax) m_code(mk, 1, bx + (k >> sh), 0, bits);
-    k = 0;
-    for (; k < gy; k++) m_code(mk, 1, by + (k >> sh), 1, bits);
-    if (gy < gmax) m_code(mk, 1, by + (k >> sh), 0, bits);
-    if (gx > 3) ibits += (gx - 2) / 2;
-    if (gy > 3) ibits += (gy - 2) / 2;
-    for (int g = cg_last - 1; g >= 1; --g) {
-      const int f = scan[g * 16];
-      const int cx = (f & (n - 1)) >> 2, cy = (f >> l2) >> 2, cb = cy * cgw + cx;
-      unsigned right = 0, lower = 0;
-      if (cx + 1 < cgw) right = cgf[cb + 1];
-      if (cy + 1 < cgw) lower = cgf[cb + cgw];
-      m_code(mg, 1, M_SIGGRP + 2 * t + ((right || lower) ? 1 : 0), cgf[cb] != 0, bits);
-    }
-    q15 += (unsigned long long)(bits * 32768.0);        // exact: a sum of table entries / 2^15
-  }
-  // with update == 0 lane 0's m_code calls above must not move the models either: m_code honours the flag
+  unsigned long long q15 = acc;       // sum of bit costs in units of 2^-15
   for (int o = 32; o >= 1; o >>= 1) {
     q15 += __shfl_xor(q15, o, 64);
     ibits += __shfl_xor(ibits, o, 64);
