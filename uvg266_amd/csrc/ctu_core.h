@@ -170,6 +170,15 @@ static int g_emul_wave = 0;      // host emulation: which wave's scratch the cod
 static int g_emul_lazy = 0;      // host emulation: pretend a CU's own cost is never known before all its children are done
 static int g_emul_depthwave = 0; // ... of its three-wave build: 32x32 / 16x16 CUs handed to the depth wave, the walk goes on into their children
 static int g_emul_leafwave = 0;  // host emulation of the P / B kernel's two-wave build: the four 4x4 CUs of an 8x8 area go to the leaf wave (ctu_pb.h)
+// Host emulation: there is one thread, so what another wave of the workgroup would do for a request happens where the request is
+// posted -- `fn` runs right here as the wave of role `w` (CTU_WAVE: that wave's scratch).  The only place that switches the wave.
+template <typename F> static inline void emul_on_wave(int w, F fn)
+{
+  const int me = g_emul_wave;
+  g_emul_wave = w;
+  fn();
+  g_emul_wave = me;
+}
 #endif
 
 enum { LCU = 64, LCU_C = 32, PY = 68, PC = 36, NMODELS = 257 };
@@ -2584,10 +2593,7 @@ template <typename PX> CTU_DEV bool help_post(lds<PX> *S, const job<PX> &J, int 
 {
   if (g_emul_lazy) return false;                   // (the host tests take both roads)
   S->help[0] = cx; S->help[1] = cy; S->help[2] = mode;
-  const int me = g_emul_wave;
-  g_emul_wave = 1;
-  help_run(S, J);
-  g_emul_wave = me;
+  emul_on_wave(1, [&] { help_run(S, J); });
   return true;
 }
 template <typename PX> CTU_DEV int help_wait(lds<PX> *S) { return S->help[3]; }
@@ -3083,13 +3089,9 @@ template <typename PX> CTU_DEV void post64(lds<PX> *S, const job<PX> &J)
 #if defined(__HIPCC__)
   SERIAL mb_store(&S->req64, 1);
 #else
-  const int me = g_emul_wave;           // host emulation: the other waves' work happens right here
   S->req64 = 1;
-  g_emul_wave = 3;
-  for (int i = 0; i < 4; ++i) luma64_step(S, J, i);
-  g_emul_wave = 2;
-  for (int i = 0; i < 4; ++i) { chroma64_step(S, J, i, 1); chroma64_step(S, J, i, 2); }
-  g_emul_wave = me;
+  emul_on_wave(3, [&] { for (int i = 0; i < 4; ++i) luma64_step(S, J, i); });
+  emul_on_wave(2, [&] { for (int i = 0; i < 4; ++i) { chroma64_step(S, J, i, 1); chroma64_step(S, J, i, 2); } });
   S->done64[0] = S->done64[1] = 1;
 #endif
 }
@@ -3170,6 +3172,13 @@ template <typename PX> CTU_DEV bool finish64(lds<PX> *S, const job<PX> &J)
 // 2002-2005); evaluating children it would have skipped changes nothing: every cut decides "not split", and so does the final
 // comparison whenever a cut would have applied (costs only grow child by child; the pruning test is re-applied when the cost is known).
 
+// the pruning test (search.c:1952-1956): with the CU's own cost N.cost known, the reference would not try its split
+CTU_INLINE CTU_DEV bool split_pruned(const params &P, const level_state &N)
+{
+  const double factor = P.qp > 30 ? 1.1 : 1.075;
+  return N.split_bits * P.lambda + N.cost / factor > N.cost;
+}
+
 // ask the wave of depth L (1..3) to evaluate the CU described by lvl[L] / pre[L] (walk's wave, lane 0 has written both)
 template <typename PX> CTU_DEV void post_eval(lds<PX> *S, const job<PX> &J, int L)
 {
@@ -3177,10 +3186,7 @@ template <typename PX> CTU_DEV void post_eval(lds<PX> *S, const job<PX> &J, int 
   CTU_SYNC();
   SERIAL mb_store(&S->req[L], S->req[L] + 1);
 #else
-  const int me = g_emul_wave;
-  g_emul_wave = 4 - L;                  // host emulation: the other wave's work happens right here
-  eval_cu(S, J, L, 1);
-  g_emul_wave = me;
+  emul_on_wave(4 - L, [&] { eval_cu(S, J, L, 1); });
   S->done[L] = ++S->req[L];
 #endif
 }
@@ -3336,8 +3342,7 @@ template <typename PX> CTU_DEV void search_ctu(lds<PX> *S, const job<PX> &J)
     // the split is complete (or was cut short): the CU's own cost is needed now
     if (N.pending) WAIT_EVAL(S, L);
     // The comparison is taken by every lane BEFORE lane 0 may overwrite a cost.
-    const double factor = P.qp > 30 ? 1.1 : 1.075;
-    const bool pruned = N.type != CU_NOTSET && N.split_bits * P.lambda + N.cost / factor > N.cost;      // the reference would not have tried the split (search.c:1952-1956)
+    const bool pruned = N.type != CU_NOTSET && split_pruned(P, N);      // the reference would not have tried the split
     const bool split_wins = !pruned && N.split_cost < N.cost;
     const int ntype = N.type;
     CTU_SYNC();
@@ -3734,7 +3739,8 @@ template <typename PX> CTU_DEV void run_ctu(lds<PX> *S, const job<PX> &J)
 #else
     coder_pass(S, J, CODER_LUMA);
     SERIAL S->vsel[CTU_WAVE] = 0;
-    { const int me = g_emul_wave; g_emul_wave = 1; coder_pass(S, J, CODER_FLAGS); g_emul_wave = 2; coder_pass(S, J, CODER_CHROMA); g_emul_wave = me; }
+    emul_on_wave(1, [&] { coder_pass(S, J, CODER_FLAGS); });
+    emul_on_wave(2, [&] { coder_pass(S, J, CODER_CHROMA); });
 #endif
     CTU_T1(J.W, 8); }
 #if defined(__HIPCC__)

@@ -1461,10 +1461,7 @@ template <typename PX> CTU_DEV void post_leaves(lds<PX> *S, const job<PX> &J)
   CTU_SYNC();
   SERIAL mb_store(&S->req[0], S->req[0] + 1);
 #else
-  const int me = g_emul_wave;
-  g_emul_wave = 1;                      // host emulation: the leaf wave's work happens right here
-  leaves_run(S, J);
-  g_emul_wave = me;
+  emul_on_wave(1, [&] { leaves_run(S, J); });          // the leaf wave's work
 #endif
 }
 template <typename PX> CTU_DEV void wait_leaves(lds<PX> *S)
@@ -1509,10 +1506,7 @@ template <typename PX> CTU_DEV void post_eval_pb(lds<PX> *S, const job<PX> &J, i
   CTU_SYNC();
   SERIAL mb_store(&S->req[mb_of(L)], S->req[mb_of(L)] + 1);
 #else
-  const int me = g_emul_wave;
-  g_emul_wave = S->depth_wave == 2 && L <= 1 ? 3 : 2;                      // host emulation: the depth wave's work happens right here
-  eval_pb(S, J, L, S->lvl[L].can & 1, S->lvl[L].can >> 1);
-  g_emul_wave = me;
+  emul_on_wave(S->depth_wave == 2 && L <= 1 ? 3 : 2, [&] { eval_pb(S, J, L, S->lvl[L].can & 1, S->lvl[L].can >> 1); });          // the depth wave's work
   S->done[mb_of(L)] = ++S->req[mb_of(L)];
 #endif
 }
@@ -1560,9 +1554,8 @@ template <typename PX> CTU_DEV void depth_worker_loop(lds<PX> *S, const job<PX> 
 template <typename PX> CTU_DEV void take_eval_pb(lds<PX> *S, const params &P, int L)
 {
   level_state &N = S->lvl[L];
-  const double factor = P.qp > 30 ? 1.1 : 1.075;
   N.known = 1;
-  N.pending = N.split_bits * P.lambda + N.cost / factor > N.cost;
+  N.pending = split_pruned(P, N);
 }
 
 // search_cu (search.c:1299-2221) of a P / B slice as a depth-first loop over the quad tree, in the reference's order
@@ -1705,15 +1698,13 @@ template <typename PX> CTU_DEV void search_ctu_pb(lds<PX> *S, const job<PX> &J)
 #if defined(__HIPCC__)
         // the CU's cost is in: what the split may cost at most before it has lost (pruned: nothing) -- the leaf wave stops there
         SERIAL {
-          const double factor = P.qp > 30 ? 1.1 : 1.075;
-          const bool pruned = N.split_bits * P.lambda + N.cost / factor > N.cost;
+          const bool pruned = split_pruned(P, N);
           __hip_atomic_store(&S->leaf_limit, pruned ? -1.0 : N.cost - N.split_bits * P.lambda, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
 #endif
         { PB_T0(); wait_leaves(S); PB_T1(J.W, 16); }
         SERIAL {
-          const double factor = P.qp > 30 ? 1.1 : 1.075;
-          N.pending = N.split_bits * P.lambda + N.cost / factor > N.cost;          // pruned (search.c:1952-1956): the reference would not have tried the split
+          N.pending = split_pruned(P, N);          // the reference would not have tried the split
           if (!N.pending)
             for (int k = 0; k < 4; ++k) {
               N.split_cost += S->leaf_cost[k];
@@ -1742,8 +1733,7 @@ template <typename PX> CTU_DEV void search_ctu_pb(lds<PX> *S, const job<PX> &J)
         double split_bits = 0;
         split_flag_bits(S, P, S->cur, 1, x, y, x & 63, y & 63, n, 1, split_bits);
         N.split_bits = split_bits;
-        const double factor = P.qp > 30 ? 1.1 : 1.075;
-        N.pending = split_bits * P.lambda + N.cost / factor > N.cost;          // pruned (search.c:1952-1956)
+        N.pending = split_pruned(P, N);
         N.split_cost = split_bits * P.lambda;
         N.child = 0;
         level_state &C = S->lvl[L + 1];
