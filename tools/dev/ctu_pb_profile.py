@@ -43,7 +43,9 @@ for f, step in enumerate(loop.steps):
     print(f"picture {f}: {len(prof)} slots, mean cycles per CTU {tot:.0f} ({tot / 1e5:.2f} ms at 100 MHz s_memtime)")
     for i, nm in enumerate(names):
         print("   %-30s %12.0f  %5.1f %%" % (nm, prof[:, i].mean(), 100 * prof[:, i].mean() / tot))
-    old = np.stack([ws[off + i * SZ + SZ - 1024: off + i * SZ + SZ].view(np.uint64).reshape(4, 32)[0] for i in range(ns.value)]).astype(np.float64)
+    old = np.stack([ws[off + i * SZ + SZ - 1024: off + i * SZ + SZ].view(np.uint64).reshape(4, 32)[0] for i in range(ns.value)])
+    old[:, 12:16] &= np.uint64((1 << 40) - 1)          # (rdoq_wave's counts stand above the cycles of these four: RQ_N; ctu_profile.py prints them)
+    old = old.astype(np.float64)
     old = old[old[:, 1].astype(bool) | old[:, 3].astype(bool)]
     onames = ["rough search", "refs+predict", "residual+transforms+recon", "RDOQ", "SSD", "RD cost bits (eval_cu)", "unpark/models", "64x64 cand", "coder", "load", "store", "total(intra)",
               "rq: candidates+last", "rq: pre-walk", "rq: decide", "rq: accumulate+group", "rq: copy-out", "rq: cbf+last search", "rq: signs", "-", "-", "-", "-", "-", "rs: setup", "rs: rough_costs",

@@ -17,7 +17,11 @@ off_order = al(512 + 32768 + ctus * 4, 256); off_pics = al(off_order + ctus * 4,
 n_slots = min(2048, al(ctus, 32))          # a slot keeps the profile of the last CTU that ran on it
 ws = cs.ws.cpu().numpy()
 SZ = 68160
-prof = np.stack([ws[off_scr + i * SZ + SZ - 1024: off_scr + i * SZ + SZ].view(np.uint64).reshape(4, 32) for i in range(n_slots)]).astype(np.float64)
+prof = np.stack([ws[off_scr + i * SZ + SZ - 1024: off_scr + i * SZ + SZ].view(np.uint64).reshape(4, 32) for i in range(n_slots)])
+rq_n = (prof[:, :, 12:16] >> np.uint64(40)).astype(np.float64)          # slots 12..15 (RQ_N): cycles in the low 40 bits, rdoq_wave's counts above them
+prof[:, :, 12:16] &= np.uint64((1 << 40) - 1)
+rq_n = rq_n[prof[:, 0, 11] > 0]
+prof = prof.astype(np.float64)
 lf = np.stack([ws[off_scr + i * SZ + SZ - 1024 - 128: off_scr + i * SZ + SZ - 1024].view(np.uint64) for i in range(n_slots)])
 runs66 = (lf[:, 10] >> np.uint64(40)).astype(np.float64)          # slot 10 (LF_TN): cycles in the low 40 bits, the number of runs above them
 lf[:, 10] &= np.uint64((1 << 40) - 1)
@@ -32,6 +36,9 @@ print("mean cycles per CTU: total %.0f (%.2f ms at 2.1 GHz)" % (tot, tot / 2.1e6
 print("%-28s %12s %12s %12s %12s" % ("", "wave0 (4x4+walk)", "wave1 (8x8)", "wave2 (16x16)", "wave3 (32x32)"))
 for i, nm in enumerate(names):
     print("  %-26s" % nm + "".join("%12.0f" % prof[:, w, i].mean() for w in range(4)))
+print("rdoq_wave of 8x8+ blocks, counts per CTU (a pass decides up to four 4x4 groups of one diagonal):")
+for i, nm in ((2, "passes"), (3, "groups decided"), (1, "passes narrowed to one group by the budget"), (0, "fixed-point rounds")):
+    print("  %-42s" % nm + "".join("%12.1f" % rq_n[:, w, i].mean() for w in range(4)))
 
 
 lfn = ["area source load", "refs (luma)", "src->sgpr, mpm, planar/DC", "pass A (modes 2..65)", "selection", "recon: refs (chroma; joint pass: + the luma prediction)", "recon: predict + residual + DCT", "recon: RDOQ", "recon: dequant + IDCT + store + SSD", "fill_cu + between the named steps", "extra pass (mode 66), where a survivor lists it", "bits: flags + mode bits (lane 0)", "bits: tr_cost (cbf + coeff_bits4)", "bits: cost + deblock marks"]

@@ -114,17 +114,20 @@
 // The phase timers of a CTU_PROFILE device build: lane 0 of the wave, s_memtime ticks.  No function body tests the switch itself.
 //   CTU_T0 / CTU_T1(W, slot)   a bracketed phase into scratch::prof[wave][slot]; PB_T0 / PB_T1: into scratch::prof_pb[slot]
 //   RQ_T0(W) ... RQ_T(slot)    consecutive phases of one function, each ending at its mark, into scratch::prof[wave][slot]
+//   RQ_N(slot, v)              a count between RQ_T0 and the marks: v above the low 40 bits of that slot's cycles (rdoq_wave: 12
+//                              fixed-point rounds, 13 passes the budget narrowed to one group, 14 passes, 15 groups decided)
 //   LF_T0() ... LF_T(slot)     the same for the 4x4 leaf on the walk's wave, into scratch::prof_lf[slot] (`J` in scope); LF_TR():
 //                              restart the interval after a step that counted itself; LF_TN(slot): a step that does not run for
 //                              every CU -- its cycles in the low 40 bits, how often it ran above them
 //   WAIT_EVAL(S, L)            wait_eval, and how long the walk stood in it, into scratch::prof_lf[14 / 15] for depths 1 + 2 / 3
 //   PB_COUNT, CTU_PROF_RESET / PB_PROF_RESET: the counters and the reset that are not a phase
-// RQ_T0 and the last group stand as statements WITHOUT a semicolon of their own: a build without the switch has no token there.
+// RQ_T0, RQ_N and the last group stand as statements WITHOUT a semicolon of their own: a build without the switch has no token there.
 #if defined(__HIPCC__) && defined(CTU_PROFILE)
 #define CTU_T0() const unsigned long long ctu_t0__ = __builtin_amdgcn_s_memtime()
 #define CTU_T1(W, slot) do { if (CTU_TID == 0) (W)->prof[CTU_WAVE][slot] += __builtin_amdgcn_s_memtime() - ctu_t0__; } while (0)
 #define RQ_T0(W) scratch *const rq_w__ = (W); unsigned long long tq = __builtin_amdgcn_s_memtime();
 #define RQ_T(slot) do { const unsigned long long t2 = __builtin_amdgcn_s_memtime(); if (CTU_TID == 0) rq_w__->prof[CTU_WAVE][slot] += t2 - tq; tq = t2; } while (0)
+#define RQ_N(slot, v) if (CTU_TID == 0) rq_w__->prof[CTU_WAVE][slot] += (unsigned long long)(v) << 40;
 #define LF_T0() unsigned long long tq = __builtin_amdgcn_s_memtime()
 #define LF_T(slot) do { const unsigned long long t2 = __builtin_amdgcn_s_memtime(); if (CTU_TID == 0 && CTU_WAVE == 0) J.W->prof_lf[slot] += t2 - tq; tq = t2; } while (0)
 #define LF_TR() do { tq = __builtin_amdgcn_s_memtime(); } while (0)          // restart: what ran since the last mark counted itself
@@ -144,6 +147,7 @@
 #define CTU_T1(W, slot) ((void)0)
 #define RQ_T0(W)
 #define RQ_T(slot) ((void)0)
+#define RQ_N(slot, v)
 #define LF_T0() ((void)0)
 #define LF_T(slot) ((void)0)
 #define LF_TR() ((void)0)
@@ -528,6 +532,12 @@ CTU_DEV void diag_order(int n, uint8_t *out)      // out[i] = y * n + x of the i
       const int y = d - x;
       if (x < n && y < n) out[i++] = (uint8_t)(y * n + x);
     }
+}
+// the index of the first position of diagonal d (x + y = d) in diag_order(n): d + 1 positions a diagonal up to the main one,
+// 2n - 1 - d beyond it
+CTU_DEV int rdoq_diag_start(int n, int d)
+{
+  return d < n ? d * (d + 1) / 2 : n * n - (2 * n - 1 - d) * (2 * n - d) / 2;
 }
 template <typename PX> CTU_DEV void build_scans(lds<PX> *S)
 {
@@ -1535,7 +1545,8 @@ template <typename DP> CTU_NOINLINE CTU_DEV rdoq_pos rdoq_decide(const rdoq_env 
 #else
 // uvg_rdoq (rdo.c:1449-1870) by one wave: same arithmetic as rdoq_serial, restructured around what is sequential in it.
 //   * every position's quantisation candidate: all positions at once;
-//   * the positions of a 4x4 group are decided together by lanes 0..15.  A decision reads only levels of positions later in scan
+//   * the positions of a 4x4 group are decided together by 16 lanes, up to four groups of one diagonal of the group grid at a time
+//     (a group per row of lanes: see the loop).  A decision reads only levels of positions later in scan
 //     order (the context template looks right / down), so the group's decisions are the unique solution of a set of equations over
 //     a DAG: the lanes start from the candidates, re-decide against each other's current levels and stop when a round changes
 //     nothing -- at that point every position holds exactly what the reference's walk leaves there (<= 8 rounds, mostly 2).
@@ -1548,6 +1559,11 @@ template <typename DP> CTU_NOINLINE CTU_DEV rdoq_pos rdoq_decide(const rdoq_env 
 CTU_DEV double rl64(double v, int lane)
 {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+  return __hiloint2double(hi, lo);
+}
+CTU_DEV double shfl64(double v, int from)
+{
+  const int lo = __shfl(__double2loint(v), from, 64), hi = __shfl(__double2hiint(v), from, 64);
   return __hiloint2double(hi, lo);
 }
 template <typename PX> CTU_INLINE1 CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W, const int16_t *coef_, int16_t *dst_, int n, int color, int cbf_u, int qp_scaled,
@@ -1625,157 +1641,190 @@ template <typename PX> CTU_INLINE1 CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W
   int reg_bins = (int)((uint32_t)(nn * 28) >> 4);
   CTU_SYNC();
   RQ_T(13);
-  double f_cc = 0, f_cs = 0, f_c0 = 0;          // cg_last == 0 (every 4x4 block, sparse larger ones): the group's numbers stay in
-  int f_lev = 0;                                 // registers for the last-position search -- no cost arrays
-  for (int cgs = cg_last; cgs >= 0; --cgs) {
-    const int first = scan[cgs * 16];
-    const int cg_pos_x = (first & (n - 1)) >> 2, cg_pos_y = (first >> l2) >> 2;
-    const int cg_blkpos = cg_pos_y * cgw + cg_pos_x;
-    const int regular = reg_bins >= 4;
-    const int scanpos = cgs * 16 + sp;
-    const bool mine = own && scanpos <= last_scanpos;
-    const int blk = scan[mine ? scanpos : cgs * 16];
-    const bool is_last = scanpos == last_scanpos;
-    const int64_t prod = (int64_t)iabs_((int)coef[blk]) * E.q;
-    const int32_t level_double = (int32_t)(prod < cap ? prod : cap);
-    const int mal0 = mine ? (int)((uint32_t)(level_double + cap_half) >> E.q_bits) : 0;
-    const double c0 = mine ? (double)level_double * (double)level_double * E.error_scale : 0.0;
-    // can the regular-bin budget run out inside this group?  (a position spends at most min(candidate, 2 -> 3) + 1 bins)
-    int fast = !regular;
-    if (regular) {
-      int bound = mine ? (mal0 < 2 ? mal0 : 3) + (is_last ? 0 : 1) : 0;
-      for (int o = 8; o >= 1; o >>= 1) bound += __shfl_xor(bound, o, 64);
-      bound = __builtin_amdgcn_readfirstlane(bound);
-      fast = reg_bins - bound >= 4;
-    }
-    double cc = 0, cs = 0;
-    int lev = 0;
-    if (fast) {
-      int go_rice = 0;
-      if (mine && regular && sp != 15 && !is_last) {
-        const int nb = scan[scanpos + 1];
-        go_rice = go_rice_par(template_abs_sum(coef, 4, nb & (n - 1), nb >> l2, n));      // sic: the INPUT coefficients (rdo.c:1697)
+  // A PASS decides up to four groups of one diagonal of the group grid, a group per row of 16 lanes: row r holds group top - r.
+  // Group (gx, gy) reads levels of itself and of (gx+1, gy), (gx, gy+1), (gx+1, gy+1) only -- the template looks right 1, 2,
+  // below 1, 2 and below-right -- and the groups of the anti-diagonal gx + gy = d hold consecutive scan indices: none of them reads
+  // another one's levels, and the groups behind them have had their zero-out.  What IS sequential across groups stays so: the
+  // sums (one group after the other below, in scan order) and the regular-bin budget, which is additive -- a pass is wide when
+  // the budget cannot run out anywhere in it (the rows' bounds together) or has run out for good; otherwise ng = 1: one group,
+  // as it was before the rows, lane 0's walk included.
+  // The loop itself runs over the groups in descending scan order: a pass where the rows have none left, then the group's sums.
+  const int row = lane >> 4;
+  double cc = 0, cs = 0, c0 = 0;                 // the numbers of the pass's positions; of the group whose sums run in lanes 0..15
+  int lev = 0, ng = 0, r = 0, counted = 0;       // (counted: the bins the groups of this pass spend leave reg_bins)
+  for (int cgs = cg_last; cgs >= 0; --cgs, ++r) {
+    if (r == ng) {
+      const int top = cgs;
+      const int ftop = scan[top * 16];
+      const int dg = ((ftop & (n - 1)) >> 2) + ((ftop >> l2) >> 2);
+      const int dstart = rdoq_diag_start(cgw, dg);          // the first scan index of top's diagonal
+      ng = top - dstart + 1 < 4 ? top - dstart + 1 : 4;
+      r = 0;
+      const int regular = reg_bins >= 4;
+      const int cgr = row < ng ? top - row : top;          // this row's group
+      const int scanpos = cgr * 16 + sp;
+      const bool mine0 = row < ng && scanpos <= last_scanpos;
+      const int blk = scan[mine0 ? scanpos : cgr * 16];
+      const bool is_last = scanpos == last_scanpos;
+      const int64_t prod = (int64_t)iabs_((int)coef[blk]) * E.q;
+      const int32_t level_double = (int32_t)(prod < cap ? prod : cap);
+      const int mal1 = (int)((uint32_t)(level_double + cap_half) >> E.q_bits);
+      // can the regular-bin budget run out inside this pass?  (a position spends at most min(candidate, 2 -> 3) + 1 bins)
+      int fast = !regular;
+      if (regular) {
+        int bound = mine0 ? (mal1 < 2 ? mal1 : 3) + (is_last ? 0 : 1) : 0;
+        for (int o = 8; o >= 1; o >>= 1) bound += __shfl_xor(bound, o, 64);          // (stays inside a row)
+        const int b0 = __builtin_amdgcn_readlane(bound, 0);
+        const int all = b0 + __builtin_amdgcn_readlane(bound, 16) + __builtin_amdgcn_readlane(bound, 32) + __builtin_amdgcn_readlane(bound, 48);
+        fast = reg_bins - all >= 4;
+        if (!fast && ng > 1) { ng = 1; fast = reg_bins - b0 >= 4; RQ_N(13, 1) }
       }
-      lev = mal0;
-      for (;;) {
-        bool changed = false;
-        if (mine) {
-          int mal;
-          const rdoq_pos r = rdoq_decide_inl(E, coef, dst, n, l2, color, blk, is_last, regular != 0, go_rice, c0, &mal);
-          cc = r.cc; cs = r.cs;
-          changed = r.level != lev;
-          lev = r.level;
+      RQ_N(14, 1) RQ_N(15, ng)
+      const bool mine = mine0 && row < ng;
+      const int mal0 = mine ? mal1 : 0;
+      c0 = mine ? (double)level_double * (double)level_double * E.error_scale : 0.0;
+      cc = 0; cs = 0;
+      lev = 0;
+      counted = fast && regular;
+      if (fast) {
+        int go_rice = 0;
+        if (mine && regular && sp != 15 && !is_last) {
+          const int nb = scan[scanpos + 1];
+          go_rice = go_rice_par(template_abs_sum(coef, 4, nb & (n - 1), nb >> l2, n));      // sic: the INPUT coefficients (rdo.c:1697)
         }
-        CTU_SYNC();                               // every lane has read the levels it needs
-        if (changed) dst[blk] = (int16_t)lev;
-        const bool any = __ballot(changed) != 0;
+        lev = mal0;
+        for (;;) {                                  // (until no lane of any row changed)
+          bool changed = false;
+          RQ_N(12, 1)
+          if (mine) {
+            int mal;
+            const rdoq_pos r = rdoq_decide_inl(E, coef, dst, n, l2, color, blk, is_last, regular != 0, go_rice, c0, &mal);
+            cc = r.cc; cs = r.cs;
+            changed = r.level != lev;
+            lev = r.level;
+          }
+          CTU_SYNC();                               // every lane has read the levels it needs
+          if (changed) dst[blk] = (int16_t)lev;
+          const bool any = __ballot(changed) != 0;
+          CTU_SYNC();
+          if (!any) break;
+        }
+      } else {
+        // the budget may run out in this group (ng == 1): position by position, exactly as the reference walks
+        if (CTU_TID == 0) {
+          int go_rice = 0, rb = reg_bins;
+          for (int k = 15; k >= 0; --k) {
+            const int spos = top * 16 + k;
+            if (spos > last_scanpos) continue;
+            const int b = scan[spos];
+            const int64_t pr = (int64_t)iabs_((int)coef[b]) * E.q;
+            const double e0 = (double)(int32_t)(pr < cap ? pr : cap);
+            int mal;
+            const rdoq_pos r = rdoq_decide(E, coef, dst, n, l2, color, b, spos == last_scanpos, rb >= 4, go_rice, e0 * e0 * E.error_scale, &mal);
+            dst[b] = (int16_t)r.level;
+            V->rq_stage[k] = r.cc; V->rq_stage[16 + k] = r.cs;
+            if ((spos % 16 == 0) && spos > 0) go_rice = 0;
+            else if (rb >= 4) {
+              rb -= (r.level < 2 ? r.level : 3) + (spos != last_scanpos);
+              go_rice = go_rice_par(template_abs_sum(coef, 4, b & (n - 1), b >> l2, n));
+            }
+          }
+          V->rq_i[4] = rb;
+        }
         CTU_SYNC();
-        if (!any) break;
+        if (mine) { cc = V->rq_stage[sp]; cs = V->rq_stage[16 + sp]; lev = dst[blk]; }
+        reg_bins = V->rq_i[4];
+        CTU_SYNC();
       }
-    } else {
-      // the budget may run out in this group: position by position, exactly as the reference walks
-      if (CTU_TID == 0) {
-        int go_rice = 0, rb = reg_bins;
-        for (int k = 15; k >= 0; --k) {
-          const int spos = cgs * 16 + k;
-          if (spos > last_scanpos) continue;
-          const int b = scan[spos];
-          const int64_t pr = (int64_t)iabs_((int)coef[b]) * E.q;
-          const double e0 = (double)(int32_t)(pr < cap ? pr : cap);
-          int mal;
-          const rdoq_pos r = rdoq_decide(E, coef, dst, n, l2, color, b, spos == last_scanpos, rb >= 4, go_rice, e0 * e0 * E.error_scale, &mal);
-          dst[b] = (int16_t)r.level;
-          V->rq_stage[k] = r.cc; V->rq_stage[16 + k] = r.cs;
-          if ((spos % 16 == 0) && spos > 0) go_rice = 0;
-          else if (rb >= 4) {
-            rb -= (r.level < 2 ? r.level : 3) + (spos != last_scanpos);
-            go_rice = go_rice_par(template_abs_sum(coef, 4, b & (n - 1), b >> l2, n));
+      RQ_T(14);
+    } else {                                      // the pass's next group: its numbers come down a row, to lanes 0..15
+      const int from = (lane + 16) & 63;
+      cc = shfl64(cc, from); cs = shfl64(cs, from); c0 = shfl64(c0, from); lev = __shfl(lev, from, 64);
+    }
+    // the sums in scan order and the group's decision (rdo.c:1689-1772): every lane, from the registers of lanes 0..15.
+    // (cc, cs, c0 and lev are zero beyond the last candidate and in rows that hold no group.)  What does not depend on the order
+    // comes from ballots: the bins spent, whether and where the group has levels.
+    {
+      const int first = scan[cgs * 16];
+      const int cg_pos_x = (first & (n - 1)) >> 2, cg_pos_y = (first >> l2) >> 2;
+      const int cg_blkpos = cg_pos_y * cgw + cg_pos_x;
+      const int gpos = cgs * 16 + sp;
+      const bool gmine = own && gpos <= last_scanpos;
+      double rd_coded = 0, rd_uncoded = 0, rd_sig = 0;
+      const unsigned m_nz = (unsigned)__ballot(lev != 0) & 0xffffu, m_gt1 = (unsigned)__ballot(lev > 1) & 0xffffu, m_mine = (unsigned)__ballot(gmine);
+      // (the first position of a group other than group 0 resets the Rice parameter INSTEAD of paying: rdo.c:1690-1697; a position
+      // pays min(level, 2 -> 3) bins and one more unless it is the last)
+      const unsigned paying = cgs ? ~1u : ~0u, not_last = cgs == cg_last ? ~(1u << (last_scanpos & 15)) : ~0u;
+      const int spent = __popc(m_nz & paying) + 2 * __popc(m_gt1 & paying) + __popc(m_mine & paying & not_last);
+      const int nnz_before_pos0 = __popc(m_nz & ~1u);
+      int flag = cgs && m_nz;
+      const bool upper = cgs < cg_last || (last_scanpos & 15) >= 8;          // (wave-uniform: the last group may end in its lower half)
+      if (cgs) {                                  // the group statistics only matter where a group can be zeroed out
+        const double dc = lev ? cc - cs : 0.0, du = lev ? c0 : 0.0;
+        if (upper) {
+#pragma unroll
+          for (int k = 15; k >= 8; --k) {
+            block_uncoded_cost += rl64(c0, k); base_cost += rl64(cc, k);
+            rd_sig += rl64(cs, k); rd_coded += rl64(dc, k); rd_uncoded += rl64(du, k);
           }
         }
-        V->rq_i[4] = rb;
-      }
-      CTU_SYNC();
-      if (mine) { cc = V->rq_stage[sp]; cs = V->rq_stage[16 + sp]; lev = dst[blk]; }
-      reg_bins = V->rq_i[4];
-      CTU_SYNC();
-    }
-    RQ_T(14);
-    // the sums in scan order and the group's decision (rdo.c:1689-1772): every lane, from the owners' registers
-    // (cc, cs, c0 and lev are zero beyond the last candidate and in lanes 16..63.)  What does not depend on the order comes from
-    // ballots: the bins spent, whether and where the group has levels.
-    double rd_coded = 0, rd_uncoded = 0, rd_sig = 0;
-    const unsigned m_nz = (unsigned)__ballot(lev != 0), m_gt1 = (unsigned)__ballot(lev > 1), m_mine = (unsigned)__ballot(mine);
-    // (the first position of a group other than group 0 resets the Rice parameter INSTEAD of paying: rdo.c:1690-1697; a position
-    // pays min(level, 2 -> 3) bins and one more unless it is the last)
-    const unsigned paying = cgs ? ~1u : ~0u, not_last = cgs == cg_last ? ~(1u << (last_scanpos & 15)) : ~0u;
-    const int spent = __popc(m_nz & paying) + 2 * __popc(m_gt1 & paying) + __popc(m_mine & paying & not_last);
-    const int nnz_before_pos0 = __popc(m_nz & ~1u);
-    int flag = cgs && m_nz;
-    const bool upper = cgs < cg_last || (last_scanpos & 15) >= 8;          // (wave-uniform: the last group may end in its lower half)
-    if (cgs) {                                  // the group statistics only matter where a group can be zeroed out
-      const double dc = lev ? cc - cs : 0.0, du = lev ? c0 : 0.0;
-      if (upper) {
 #pragma unroll
-        for (int k = 15; k >= 8; --k) {
+        for (int k = 7; k >= 0; --k) {
           block_uncoded_cost += rl64(c0, k); base_cost += rl64(cc, k);
           rd_sig += rl64(cs, k); rd_coded += rl64(dc, k); rd_uncoded += rl64(du, k);
         }
-      }
+      } else {
+        if (upper) {
 #pragma unroll
-      for (int k = 7; k >= 0; --k) {
-        block_uncoded_cost += rl64(c0, k); base_cost += rl64(cc, k);
-        rd_sig += rl64(cs, k); rd_coded += rl64(dc, k); rd_uncoded += rl64(du, k);
-      }
-    } else {
-      if (upper) {
-#pragma unroll
-        for (int k = 15; k >= 8; --k) { block_uncoded_cost += rl64(c0, k); base_cost += rl64(cc, k); }
-      }
-#pragma unroll
-      for (int k = 7; k >= 0; --k) { block_uncoded_cost += rl64(c0, k); base_cost += rl64(cc, k); }
-    }
-    const double rd_sig0 = rl64(cs, 0);
-    if (fast && regular) reg_bins -= spent;
-    int zeroed = 0;
-    if (cgs) {
-      unsigned right = 0, lower = 0;
-      if (cg_pos_x + 1 < cgw) right = V->cg_flag[cg_blkpos + 1];
-      if (cg_pos_y + 1 < cgw) lower = V->cg_flag[cg_blkpos + cgw];
-      const int o_grp = M_SIGGRP + (E.t ? 2 : 0) + ((right || lower) ? 1 : 0);
-      double cgc = 0;
-      if (!flag) {
-        cgc = lambda * rbits(E, o_grp, 0);
-        base_cost += cgc - rd_sig;
-      } else if (cgs < cg_last) {
-        if (nnz_before_pos0 == 0) { base_cost -= rd_sig0; rd_sig -= rd_sig0; }
-        double cost_zero_cg = base_cost;
-        cgc = lambda * rbits(E, o_grp, 1);
-        base_cost += cgc;
-        cost_zero_cg += lambda * rbits(E, o_grp, 0);
-        cost_zero_cg += rd_uncoded;
-        cost_zero_cg -= rd_coded;
-        cost_zero_cg -= rd_sig;
-        if (cost_zero_cg < base_cost) {
-          flag = 0;
-          zeroed = 1;
-          base_cost = cost_zero_cg;
-          cgc = lambda * rbits(E, o_grp, 0);
+          for (int k = 15; k >= 8; --k) { block_uncoded_cost += rl64(c0, k); base_cost += rl64(cc, k); }
         }
+#pragma unroll
+        for (int k = 7; k >= 0; --k) { block_uncoded_cost += rl64(c0, k); base_cost += rl64(cc, k); }
       }
-      CTU_SYNC();                                 // (the neighbours' flags are read)
-      if (CTU_TID == 0) cost_cg_sig[cgs] = cgc;
-    } else {
-      flag = 1;
+      const double rd_sig0 = rl64(cs, 0);
+      if (counted) reg_bins -= spent;
+      int zeroed = 0;
+      if (cgs) {
+        unsigned right = 0, lower = 0;
+        if (cg_pos_x + 1 < cgw) right = V->cg_flag[cg_blkpos + 1];
+        if (cg_pos_y + 1 < cgw) lower = V->cg_flag[cg_blkpos + cgw];
+        const int o_grp = M_SIGGRP + (E.t ? 2 : 0) + ((right || lower) ? 1 : 0);
+        double cgc = 0;
+        if (!flag) {
+          cgc = lambda * rbits(E, o_grp, 0);
+          base_cost += cgc - rd_sig;
+        } else if (cgs < cg_last) {
+          if (nnz_before_pos0 == 0) { base_cost -= rd_sig0; rd_sig -= rd_sig0; }
+          double cost_zero_cg = base_cost;
+          cgc = lambda * rbits(E, o_grp, 1);
+          base_cost += cgc;
+          cost_zero_cg += lambda * rbits(E, o_grp, 0);
+          cost_zero_cg += rd_uncoded;
+          cost_zero_cg -= rd_coded;
+          cost_zero_cg -= rd_sig;
+          if (cost_zero_cg < base_cost) {
+            flag = 0;
+            zeroed = 1;
+            base_cost = cost_zero_cg;
+            cgc = lambda * rbits(E, o_grp, 0);
+          }
+        }
+        CTU_SYNC();                                 // (the neighbours' flags are read)
+        if (CTU_TID == 0) cost_cg_sig[cgs] = cgc;
+      } else {
+        flag = 1;
+      }
+      if (CTU_TID == 0) V->cg_flag[cg_blkpos] = (uint8_t)flag;
+      // the group's costs go to the per-position arrays the last-position search reads; a zeroed group's positions fall back to level 0
+      // (cg_last == 0 -- sparse blocks: the one group's numbers stay where they are, in cc, cs, c0 and lev, for the last-position
+      // search: no cost arrays)
+      if (cg_last != 0 && gmine) {
+        const double wc = (zeroed && lev) ? c0 : cc, ws = (zeroed && lev) ? 0.0 : cs;
+        if (zeroed && lev) dst[scan[gpos]] = 0;
+        if (small) { CCl[gpos] = wc; CSl[gpos] = ws; } else { CCg[gpos] = wc; CSg[gpos] = ws; }
+      }
+      CTU_SYNC();
     }
-    if (CTU_TID == 0) V->cg_flag[cg_blkpos] = (uint8_t)flag;
-    // the group's costs go to the per-position arrays the last-position search reads; a zeroed group's positions fall back to level 0
-    if (cg_last == 0) { f_cc = cc; f_cs = cs; f_c0 = c0; f_lev = lev; }
-    else if (mine) {
-      const double wc = (zeroed && lev) ? c0 : cc, ws = (zeroed && lev) ? 0.0 : cs;
-      if (zeroed && lev) dst[blk] = 0;
-      if (small) { CCl[scanpos] = wc; CSl[scanpos] = ws; } else { CCg[scanpos] = wc; CSg[scanpos] = ws; }
-    }
-    CTU_SYNC();
     RQ_T(15);
   }
   RQ_T(16);
@@ -1798,12 +1847,12 @@ template <typename PX> CTU_INLINE1 CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W
     const int scanpos = cgs * 16 + sp;
     const bool mine = own && scanpos <= last_scanpos;
     const int blkpos = scan[mine ? scanpos : cgs * 16];
-    const int lev = cg_last == 0 ? f_lev : (mine ? (int)dst[blkpos] : 0);
+    const int klev = cg_last == 0 ? lev : (mine ? (int)dst[blkpos] : 0);
     double kcs = 0, kcc = 0, k0 = 0, klast = 0;
     if (mine) {
-      kcs = cg_last == 0 ? f_cs : (small ? CSl[scanpos] : CTU_GLOAD(&CSg[scanpos]));
-      if (lev) {
-        if (cg_last == 0) { kcc = f_cc; k0 = f_c0; }
+      kcs = cg_last == 0 ? cs : (small ? CSl[scanpos] : CTU_GLOAD(&CSg[scanpos]));
+      if (klev) {
+        if (cg_last == 0) { kcc = cc; k0 = c0; }
         else {
           kcc = small ? CCl[scanpos] : CTU_GLOAD(&CCg[scanpos]);
           const int64_t prod = (int64_t)iabs_((int)coef[blkpos]) * E.q;
@@ -1822,8 +1871,8 @@ template <typename PX> CTU_INLINE1 CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W
     // of equal totals in descending order wins; then its level's cost leaves base_cost and its level-0 cost comes back, while a
     // zero's significance flag leaves it (and +0.0 comes back: k0 is zero there).  The walk ends at the first level above 1: known
     // from a ballot, the positions below it are no candidates and base_cost is not read again.
-    const double kx = lev ? kcc : kcs;
-    const unsigned m_nz = (unsigned)__ballot(lev != 0), m_gt1 = (unsigned)__ballot(lev > 1);
+    const double kx = klev ? kcc : kcs;
+    const unsigned m_nz = (unsigned)__ballot(klev != 0), m_gt1 = (unsigned)__ballot(klev > 1);
     const int kstop = m_gt1 ? 31 - __clz(m_gt1) : 0;
     const unsigned cand = m_nz >> kstop << kstop;
     if (cgs < cg_last || (last_scanpos & 15) >= 8) {              // (wave-uniform, as is kstop < 8 below)
