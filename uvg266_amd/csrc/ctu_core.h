@@ -51,9 +51,9 @@
 //   switch        what it changes
 //   __HIPCC__     64 lanes and wave fences instead of one lane (the macros below); the 4x4 leaf on ctu_leaf4.h (lds::lf_*, eval_cu4,
 //                 coder_area4, a 4x4 arena share without the rough search's and RDOQ's arrays) -- the host keeps eval_cu for it;
-//                 its own rdoq_wave (the host's: ctu_rdoq_emul.h), rough_costs and search_intra_rough (the selection in the lanes'
-//                 registers, rs_round; the host's goes through wctx::rs_*); the depth waves' mailboxes instead of calls in
-//                 place; the slim images: lds_cfg<uint16_t>::slim of the intra kernel (cand_px, the 32x32 arena share and the two
+//                 the wave-level rdoq_wave, coeff_bits, rough_costs and search_intra_rough (the selection in the lanes' registers,
+//                 rs_round) -- the host's are the reference's serial walks (rdoq_serial in ctu_rdoq_emul.h, coeff_bits_serial, a three-entry list in
+//                 locals); the depth waves' mailboxes instead of calls in place; the slim images: lds_cfg<uint16_t>::slim of the intra kernel (cand_px, the 32x32 arena share and the two
 //                 large scans in the workgroup's global scratch), lds_cfg<PX>::slim_scan with CTU_PB (the scans only)
 //   CTU_PB        NMX = 257 + 18 models per set; level_state::mot / fl / cbf4; wctx::rq_root; lds::pb .. cur64 (the inter state, the
 //                 leaf and depth waves' own) in place of lds::req64 .. h64 (the 64x64 candidate beside the walk, the coder's pass
@@ -254,11 +254,11 @@ struct wctx {
   uint32_t *cur;                                    // the models this wave's bit counting works on
   union {                                           // a wave is in one phase at a time
     double rq_stage[2 * 16];                        // RDOQ: costs of the coefficient group in flight (also the coefficient bit count's 64 group totals)
-    struct { double rs_cand[3 + 24], rs_best_cost[2][3]; };      // rough search: costs of the survivors and of the listed modes; the survivors, double-buffered
-  };
-  double u_d0, u_d1;
+    struct { double rs_cand[3 + 24], rs_best_cost[2][3]; };      // rough search: [0] the winner's cost.  The rest, like u_d0, u_d1, rs_best_mode,
+  };                                                // rs_chk, u_n_modes and lds::help below, has no reader or writer in any build: the layout was kept
+  double u_d0, u_d1;                                // when the host emulation stopped using them (profiles/README.md, r14)
   int32_t rq_i[16];
-  int32_t rs_list[24], rs_best_mode[2][3];
+  int32_t rs_list[24], rs_best_mode[2][3];          // rs_list: the modes listed in the round (rough_costs reads it)
   uint32_t rs_chk[3];
   int32_t red[8];
   int32_t u_avail_left, u_avail_top, u_mode, u_flag, u_n_modes;
@@ -355,7 +355,7 @@ template <typename PX> struct lds {
   int32_t vsel[4];                                  // which wv[] a wave is using (a wave may borrow a larger one while its owner idles)
   int32_t rot;                                      // index of the wave with role 0 (CTU_WAVE)
   int32_t req[4], done[4];                          // depth pipeline: evaluation requests / completions per depth
-  int32_t help[4];                                  // the host emulation's chroma helper (help_post): area x, y, mode -> has_coeffs
+  int32_t help[4];                                  // unused (see wctx::rs_cand)
 #if defined(__HIPCC__)
   // ctu_leaf4.h: the cubic interpolation filter (4 x int8 per phase), intraPredAngle | invAngle << 8 per |mode distance|, per raster
   // position of a 4x4 block (positions later in scan order | scan index << 16 | raster of the next scan index << 20), the 8x8 area
@@ -964,7 +964,7 @@ template <typename PX> CTU_DEV void mpm_neighbours(lds<PX> *S, int x, int y, int
 // Device: a lane per listed mode keeps the mode's cost in its registers and the three survivors are wave-uniform values -- the
 // minima of a round's newcomers are taken one at a time and inserted the way the reference inserts (rs_round), the
 // next round's list is derived in the lanes 0..5, a lane per try.  Only the list itself goes through LDS (rough_costs reads it).
-// The host emulation below keeps the general formulation through the LDS arrays; the two agree only if this one is right.
+// The host emulation below is the reference's serial walk; the two agree only if this one is right.
 template <typename PX> CTU_INLINE1 CTU_DEV void search_intra_rough(lds<PX> *S, const job<PX> &J, int x, int y, int lx, int ly, int n)
 {
   wctx *const V = wv_of(S);
@@ -1047,105 +1047,64 @@ template <typename PX> CTU_INLINE1 CTU_DEV void search_intra_rough(lds<PX> *S, c
   RQ_T(27);
 }
 #else
+// Host: the reference's walk as it stands (search_intra.c:1071-1215) -- one candidate at a time into a three-entry list.
 template <typename PX> CTU_INLINE1 CTU_DEV void search_intra_rough(lds<PX> *S, const job<PX> &J, int x, int y, int lx, int ly, int n)
 {
   wctx *const V = wv_of(S);
   const params &P = J.P;
   const int T = n >= 8 ? 8 : 4, tiles = (n / T) * (n / T);
-  RQ_T0(J.W)
-  SERIAL {
-    const cu4 *l, *a;
-    mpm_neighbours(S, x, y, lx, ly, n, &l, &a);
-    dir_luma_predictor(y, V->mpm, l, a);
-    const int offset = 1 << P.rough_levels;
-    int k = 0;
-    uint32_t h0 = 3, h1 = 0, h2 = 0;            // modes costed so far
-    V->rs_list[k++] = 0; V->rs_list[k++] = 1;
-    for (int mode = 2 + offset / 2; mode <= 66; mode += 2 * offset)
-      for (int i = 0; i < 2; ++i) {
-        const int m = mode + i * offset;
-        if (m > 66) continue;
-        V->rs_list[k++] = m;
-        const uint32_t bit = 1u << (m & 31);
-        if (m < 32) h0 |= bit; else if (m < 64) h1 |= bit; else h2 |= bit;
-      }
-    V->rs_chk[0] = h0; V->rs_chk[1] = h1; V->rs_chk[2] = h2;
-    V->u_n_modes = k;
-  }
-  CTU_SYNC();
-  RQ_T(24);
-  // (rs_list holds at most 18 entries with rough_levels >= 2; the host refuses smaller values)
-  // The reference inserts every costed mode into a three-entry list with a strict "<" (search_intra.c:1071-1143), i.e. the list is
-  // the three smallest of everything costed so far under the order (cost, insertion sequence); DC is inserted ahead of planar when
-  // the two tie (:1089-1106).  Here a lane per candidate counts the candidates ahead of it -- no loop-carried list.
+  const cu4 *l, *a;
+  mpm_neighbours(S, x, y, lx, ly, n, &l, &a);
+  dir_luma_predictor(y, V->mpm, l, a);
+  const double mpm_bit = m_fbits(V->cur, M_MPM, 1), not_mpm_bit = m_fbits(V->cur, M_MPM, 0);
+  const double planar = m_fbits(V->cur, M_PLANAR + 1, 0), not_planar = m_fbits(V->cur, M_PLANAR + 1, 1);
+  // round 0's list: planar, DC, every 2^levels-th angular mode from 2 + 2^levels / 2 (18 entries with rough_levels >= 2; the host
+  // refuses smaller values)
   int offset = 1 << P.rough_levels;
+  int32_t list[24];
+  bool listed[67] = {};
+  int nm = 0;
+  list[nm++] = 0; list[nm++] = 1;
+  for (int m = 2 + offset / 2; m <= 66; m += offset) list[nm++] = m;
+  for (int i = 0; i < nm; ++i) listed[list[i]] = true;
+  double best_cost[3] = {CTU_MAX_DOUBLE, CTU_MAX_DOUBLE, CTU_MAX_DOUBLE};
+  int best_mode[3] = {0, 0, 0};
+  bool differs = false;
   for (int round = 0;; ++round) {
-    rough_costs(S, J, lx, ly, n, V->rs_list, V->u_n_modes);
-    RQ_T(25);
-    const int nm = V->u_n_modes;
-    CTU_LDS const uint32_t *const mdl = LDSP(const uint32_t, V->cur), *const part = LDSP(const uint32_t, V->part);
-    PAR_FOR(mi, nm) {                           // a lane per mode: tile sums, bit cost (count_bits reads the four flag costs itself)
-      const double mpm_bit = m_fbits(mdl, M_MPM, 1), not_mpm_bit = m_fbits(mdl, M_MPM, 0);
-      const double planar = m_fbits(mdl, M_PLANAR + 1, 0), not_planar = m_fbits(mdl, M_PLANAR + 1, 1);
-      const int mode = V->rs_list[mi];
+    rough_costs(S, J, lx, ly, n, list, nm);
+    double cost[24];
+    for (int mi = 0; mi < nm; ++mi) {           // tile sums, bit cost
       unsigned satd = 0, sad = 0;
-      for (int t = 0; t < tiles; ++t) { satd += part[2 * (mi * tiles + t)]; sad += part[2 * (mi * tiles + t) + 1]; }
+      for (int t = 0; t < tiles; ++t) { satd += V->part[2 * (mi * tiles + t)]; sad += V->part[2 * (mi * tiles + t) + 1]; }
       if (n >= 8) satd >>= (px_info<PX>::depth - 8);       // satd_NxN shifts, the 4x4 function does not (picture-generic.c:170)
       sad >>= (px_info<PX>::depth - 8);
-      double c = (double)(satd < sad * 2 ? satd : sad * 2);
-      c += count_bits(V->mpm, planar, not_planar, mpm_bit, not_mpm_bit, mode) * P.lambda_sqrt;
-      V->rs_cand[3 + mi] = c;
+      cost[mi] = (double)(satd < sad * 2 ? satd : sad * 2) + count_bits(V->mpm, planar, not_planar, mpm_bit, not_mpm_bit, list[mi]) * P.lambda_sqrt;
+      if (round == 0) differs = differs || cost[mi] != cost[0];          // min_cost != max_cost (:1082-1143): only the first round moves them
     }
-    CTU_SYNC();
-    RQ_T(26);
-    // candidates: the survivors so far (sequence 0..2, rounds > 0), then the listed modes (sequence 3 + index; round 0: DC 0, planar 1)
-    const int first = round ? 0 : 3;
-    const int cur = round & 1;
-    PAR_FOR(ci0, nm + 3 - first) {
-      const int ci = ci0 + first;
-      const double c = V->rs_cand[ci];
-      const int seq = (round == 0 && ci < 5) ? 4 - ci : ci;
-      int rank = 0, differs = 0;
-      const double c_first = V->rs_cand[first];
-      for (int cj = first; cj < nm + 3; ++cj) {
-        const double o = V->rs_cand[cj];
-        const int oseq = (round == 0 && cj < 5) ? 4 - cj : cj;
-        rank += (o < c || (o == c && oseq < seq)) ? 1 : 0;
-        differs |= o != c_first;
-      }
-      if (rank < 3) { V->rs_best_mode[cur][rank] = ci < 3 ? V->rs_best_mode[cur ^ 1][ci] : V->rs_list[ci - 3]; V->rs_best_cost[cur][rank] = c; }
-      if (round == 0 && ci0 == 0) V->u_flag = differs;          // min_cost != max_cost (:1082-1143): only the first round moves them
+    for (int i = 0; i < nm; ++i) {
+      const int mi = (round == 0 && i < 2) ? 1 - i : i;                  // DC ahead of planar (:1089-1106)
+      for (int j = 0; j < 3; ++j)
+        if (cost[mi] < best_cost[j]) {
+          for (int k = 2; k > j; --k) { best_cost[k] = best_cost[k - 1]; best_mode[k] = best_mode[k - 1]; }
+          best_cost[j] = cost[mi]; best_mode[j] = list[mi];
+          break;
+        }
     }
-    CTU_SYNC();
-    SERIAL {
-      // next round's list (search_intra.c:1146-1215)
-      const int b0 = V->rs_best_mode[cur][0], b1 = V->rs_best_mode[cur][1], b2 = V->rs_best_mode[cur][2];
-      const double k0 = V->rs_best_cost[cur][0], k1 = V->rs_best_cost[cur][1], k2 = V->rs_best_cost[cur][2];
-      uint32_t h0 = V->rs_chk[0], h1 = V->rs_chk[1], h2 = V->rs_chk[2];
-      const int go = (offset >> 1) > 0 && V->u_flag;
-      int k = 0;
-      if (go) {
-        const int off = offset >> 1;
-#define CTU_TRY(m_) do { const int m = (m_); if (m >= 2 && m <= 66) { const uint32_t bit = 1u << (m & 31); const uint32_t w = m < 32 ? h0 : (m < 64 ? h1 : h2); \
-          if (!(w & bit)) { V->rs_list[k++] = m; if (m < 32) h0 |= bit; else if (m < 64) h1 |= bit; else h2 |= bit; } } } while (0)
-        if (b0 >= 3 && b0 <= 65) { CTU_TRY(b0 - off); CTU_TRY(b0 + off); }
-        if (b1 >= 3 && b1 <= 65) { CTU_TRY(b1 - off); CTU_TRY(b1 + off); }
-        if (b2 >= 3 && b2 <= 65) { CTU_TRY(b2 - off); CTU_TRY(b2 + off); }
-#undef CTU_TRY
-      }
-      V->rs_chk[0] = h0; V->rs_chk[1] = h1; V->rs_chk[2] = h2;
-      V->rs_cand[0] = k0; V->rs_cand[1] = k1; V->rs_cand[2] = k2;
-      V->u_n_modes = k;
-      V->u_d0 = go;
-      V->u_mode = b0;
-    }
+    // next round's list (:1146-1215): b -+ offset of each survivor in 3..65; a mode is listed where it is first tried and only if it
+    // was never listed.  An empty list still runs the remaining rounds.
     offset >>= 1;
-    CTU_SYNC();
-    RQ_T(27);
-    if (V->u_d0 == 0) break;
+    if (!(offset > 0 && differs)) break;
+    nm = 0;
+    for (int j = 0; j < 3; ++j) {
+      const int b = best_mode[j];
+      if (b < 3 || b > 65) continue;
+      for (int m = b - offset; m <= b + offset; m += 2 * offset)
+        if (m >= 2 && m <= 66 && !listed[m]) { listed[m] = true; list[nm++] = m; }
+    }
   }
+  V->u_mode = best_mode[0];
+  V->rs_cand[0] = best_cost[0];
 }
-
 #endif
 
 // ---------------------------------------------------------------------------------------------------- transforms ------
@@ -1317,197 +1276,6 @@ __device__ static const int16_t kQuantScales[6] = {26214, 23302, 20560, 18396, 1
 __device__ static const int16_t kInvQuantScales[6] = {40, 45, 51, 57, 64, 72};                     // uvg_g_inv_quant_scales[0]
 __device__ static const double kPow2[16] = {1.0, 2.0, 4.0, 8.0, 16.0, 32.0, 64.0, 128.0, 256.0, 512.0, 1024.0, 2048.0, 4096.0, 8192.0, 16384.0, 32768.0};
 
-// uvg_rdoq (rdo.c:1449-1870) of an n x n block (square: no sqrt2 scaling), intra, no LFNST / MTS / sign hiding; lane 0 only.
-// coef -> levels in dst (both n * n, raster).  Returns whether any level survived.
-CTU_NOINLINE CTU_DEV int rdoq_serial(const uint8_t *st, const uint16_t *scan, scratch *W, const int16_t *coef, int16_t *dst, int n, int color, int cbf_u,
-                        int qp_scaled, double lambda, int bitdepth)
-{
-  const int l2 = ilog2_dev(n);
-  rdoq_env E;
-  E.st = st; E.t = color ? 1 : 0; E.lambda = lambda;
-  const int transform_shift = 15 - bitdepth - l2;
-  uint32_t reg_bins = (uint32_t)(n * n * 28) >> 4;
-  E.q_bits = 14 + qp_scaled / 6 + transform_shift;
-  const int32_t q = kQuantScales[qp_scaled % 6];
-  // scale = 32768 * 2^(-2 * transform_shift) (rdo.c:1527: pow() of an integer exponent, exact), error_scale = scale / q / q
-  double scale = 32768;
-  scale = transform_shift >= 0 ? scale / kPow2[2 * transform_shift] : scale * kPow2[-2 * transform_shift];
-  E.error_scale = scale / q / q;
-  double *cost_coeff = W->cost_coeff, *cost_sig = W->cost_sig, *cost_coeff0 = W->cost_coeff0;
-  double block_uncoded_cost = 0, base_cost = 0;
-  const int cg_num = (n * n) >> 4, cgw = n >> 2;
-  double cost_cg_sig[64];
-  uint8_t cg_flag[64];
-  uint8_t lv_spend[1024];                           // coefficient bit cost: regular bins a scan position spends
-  for (int i = 0; i < cg_num; ++i) cg_flag[i] = 0;
-  for (int i = 0; i < n * n; ++i) dst[i] = 0;
-  int ctx_set = 0, temp_diag = -1, temp_sum = -1;
-  int go_rice = 0;
-  int cg_last_scanpos = -1, last_scanpos = -1;
-  const int cap_half = 1 << (E.q_bits - 1);
-  int cgs;
-  for (cgs = cg_num - 1; cgs >= 0; cgs--) {
-    for (int sp = 15; sp >= 0; sp--) {
-      const int scanpos = cgs * 16 + sp;
-      const int blkpos = scan[scanpos];
-      const int64_t prod = (int64_t)iabs_((int)coef[blkpos]) * q;
-      const int32_t cap = 0x7fffffff - cap_half;
-      const int32_t level_double = (int32_t)(prod < cap ? prod : cap);
-      const uint32_t max_abs_level = (uint32_t)(level_double + cap_half) >> E.q_bits;
-      const double err = (double)level_double;
-      cost_coeff0[scanpos] = err * err * E.error_scale;
-      dst[blkpos] = (int16_t)max_abs_level;
-      if (max_abs_level > 0) { last_scanpos = scanpos; cg_last_scanpos = cgs; break; }
-      block_uncoded_cost += cost_coeff0[scanpos];
-      base_cost += cost_coeff0[scanpos];
-    }
-    if (last_scanpos != -1) break;
-  }
-  if (last_scanpos == -1) return 0;
-  for (; cgs >= 0; cgs--) cost_cg_sig[cgs] = 0;
-
-  for (cgs = cg_last_scanpos; cgs >= 0; cgs--) {
-    // the group's raster index = position of its first coefficient / 4
-    const int first = scan[cgs * 16];
-    const int cg_pos_x = (first & (n - 1)) >> 2, cg_pos_y = (first >> l2) >> 2;
-    const int cg_blkpos = cg_pos_y * cgw + cg_pos_x;
-    double rd_coded = 0, rd_uncoded = 0, rd_sig = 0, rd_sig0 = 0;
-    int nnz_before_pos0 = 0;
-    for (int sp = 15; sp >= 0; sp--) {
-      const int scanpos = cgs * 16 + sp;
-      if (scanpos > last_scanpos) continue;
-      const int blkpos = scan[scanpos];
-      const int64_t prod = (int64_t)iabs_((int)coef[blkpos]) * q;
-      const int32_t cap = 0x7fffffff - cap_half;
-      const int32_t level_double = (int32_t)(prod < cap ? prod : cap);
-      const uint32_t max_abs_level = (uint32_t)(level_double + cap_half) >> E.q_bits;
-      dst[blkpos] = (int16_t)max_abs_level;
-      const double err = (double)level_double;
-      cost_coeff0[scanpos] = err * err * E.error_scale;
-      block_uncoded_cost += cost_coeff0[scanpos];
-      {
-        const int pos_y = blkpos >> l2, pos_x = blkpos - (pos_y << l2);
-        int ctx_sig = 0;
-        if (scanpos != last_scanpos) ctx_sig = sig_ctx_abs(dst, pos_x, pos_y, n, color, &temp_diag, &temp_sum);
-        if (temp_diag != -1)
-          ctx_set = ((temp_sum < 4 ? temp_sum : 4) + 1) +
-                    (!temp_diag ? ((color == 0) ? 15 : 5) : (color == 0) ? (temp_diag < 3 ? 10 : (temp_diag < 10 ? 5 : 0)) : 0);
-        else ctx_set = 0;
-        if (reg_bins < 4) go_rice = go_rice_par(template_abs_sum(dst, 0, pos_x, pos_y, n));
-        const int level = (int)coded_level(E, &cost_coeff[scanpos], cost_coeff0[scanpos], &cost_sig[scanpos], level_double, max_abs_level,
-                                           scanpos == last_scanpos ? 0 : ctx_sig, ctx_set, go_rice, reg_bins, scanpos == last_scanpos);
-        dst[blkpos] = (int16_t)level;
-        base_cost += cost_coeff[scanpos];
-        if ((scanpos % 16 == 0) && scanpos > 0) go_rice = 0;
-        else if (reg_bins >= 4) {
-          reg_bins -= (uint32_t)((level < 2 ? level : 3) + (scanpos != last_scanpos));
-          go_rice = go_rice_par(template_abs_sum(coef, 4, pos_x, pos_y, n));       // sic: the INPUT coefficients (rdo.c:1697)
-        }
-      }
-      rd_sig += cost_sig[scanpos];
-      if (sp == 0) rd_sig0 = cost_sig[scanpos];
-      if (dst[blkpos]) {
-        cg_flag[cg_blkpos] = 1;
-        rd_coded += cost_coeff[scanpos] - cost_sig[scanpos];
-        rd_uncoded += cost_coeff0[scanpos];
-        if (sp != 0) nnz_before_pos0++;
-      }
-    }
-    if (cgs) {
-      unsigned right = 0, lower = 0;
-      if (cg_pos_x + 1 < cgw) right = cg_flag[cg_blkpos + 1];
-      if (cg_pos_y + 1 < cgw) lower = cg_flag[cg_blkpos + cgw];
-      const int o_grp = M_SIGGRP + (E.t ? 2 : 0) + ((right || lower) ? 1 : 0);
-      if (cg_flag[cg_blkpos] == 0) {
-        cost_cg_sig[cgs] = lambda * rbits(E, o_grp, 0);
-        base_cost += cost_cg_sig[cgs] - rd_sig;
-      } else if (cgs < cg_last_scanpos) {
-        if (nnz_before_pos0 == 0) { base_cost -= rd_sig0; rd_sig -= rd_sig0; }
-        double cost_zero_cg = base_cost;
-        cost_cg_sig[cgs] = lambda * rbits(E, o_grp, 1);
-        base_cost += cost_cg_sig[cgs];
-        cost_zero_cg += lambda * rbits(E, o_grp, 0);
-        cost_zero_cg += rd_uncoded;
-        cost_zero_cg -= rd_coded;
-        cost_zero_cg -= rd_sig;
-        if (cost_zero_cg < base_cost) {
-          cg_flag[cg_blkpos] = 0;
-          base_cost = cost_zero_cg;
-          cost_cg_sig[cgs] = lambda * rbits(E, o_grp, 0);
-          for (int sp = 15; sp >= 0; sp--) {
-            const int scanpos = cgs * 16 + sp;
-            const int blkpos = scan[scanpos];
-            if (dst[blkpos]) { dst[blkpos] = 0; cost_coeff[scanpos] = cost_coeff0[scanpos]; cost_sig[scanpos] = 0; }
-          }
-        }
-      }
-    } else {
-      cg_flag[cg_blkpos] = 1;
-    }
-  }
-
-  double best_cost;
-  int best_last_idx_p1 = 0;
-  {
-    const int o_cbf = color == 0 ? M_CBF_LUMA : color == 1 ? M_CBF_CB : M_CBF_CR + (cbf_u ? 1 : 0);
-    best_cost = block_uncoded_cost + lambda * rbits(E, o_cbf, 0);
-    base_cost += lambda * rbits(E, o_cbf, 1);
-  }
-  // calc_last_bits (rdo.c:664-700)
-  int32_t last_x_bits[32], last_y_bits[32];
-  {
-    const int prefix_ctx[8] = {0, 0, 0, 3, 6, 10, 15, 21};
-    const int off = E.t ? 0 : prefix_ctx[l2];
-    const int sh = E.t ? clampi(n >> 3, 0, 2) : ((l2 + 1) >> 2);
-    int32_t bx = 0, by = 0;
-    int ctx;
-    for (ctx = 0; ctx < group_idx(n - 1); ctx++) {
-      const int o = off + (ctx >> sh);
-      const int mx = M_LASTX + (E.t ? 20 : 0) + o, my = M_LASTY + (E.t ? 20 : 0) + o;
-      last_x_bits[ctx] = bx + rbits(E, mx, 0); bx += rbits(E, mx, 1);
-      last_y_bits[ctx] = by + rbits(E, my, 0); by += rbits(E, my, 1);
-    }
-    last_x_bits[ctx] = bx; last_y_bits[ctx] = by;
-  }
-  int found_last = 0;
-  for (cgs = cg_last_scanpos; cgs >= 0; cgs--) {
-    const int first = scan[cgs * 16];
-    const int cg_blkpos = ((first >> l2) >> 2) * cgw + ((first & (n - 1)) >> 2);
-    base_cost -= cost_cg_sig[cgs];
-    if (cg_flag[cg_blkpos]) {
-      for (int sp = 15; sp >= 0; sp--) {
-        const int scanpos = cgs * 16 + sp;
-        if (scanpos > last_scanpos) continue;
-        const int blkpos = scan[scanpos];
-        if (dst[blkpos]) {
-          const int pos_y = blkpos >> l2, pos_x = blkpos - (pos_y << l2);
-          const int cx = group_idx(pos_x), cy = group_idx(pos_y);
-          double cl = last_x_bits[cx] + last_y_bits[cy];
-          if (cx > 3) cl += 32768 * ((cx - 2) >> 1);
-          if (cy > 3) cl += 32768 * ((cy - 2) >> 1);
-          const double cost_last = lambda * cl;
-          const double total = base_cost + cost_last - cost_sig[scanpos];
-          if (total < best_cost) { best_last_idx_p1 = scanpos + 1; best_cost = total; }
-          if (dst[blkpos] > 1) { found_last = 1; break; }
-          base_cost -= cost_coeff[scanpos];
-          base_cost += cost_coeff0[scanpos];
-        } else {
-          base_cost -= cost_sig[scanpos];
-        }
-      }
-      if (found_last) break;
-    }
-  }
-  int any = 0;
-  for (int scanpos = 0; scanpos < best_last_idx_p1; scanpos++) {
-    const int b = scan[scanpos], level = dst[b];
-    any |= level;
-    dst[b] = (int16_t)((coef[b] < 0) ? -level : level);
-  }
-  for (int scanpos = best_last_idx_p1; scanpos <= last_scanpos; scanpos++) dst[scan[scanpos]] = 0;
-  return any != 0;
-}
-
 // one position of uvg_rdoq's main walk (rdo.c:1600-1716): the level that survives, its cost and the cost of its significance flag.
 // regular: regular bins remain (reg_bins >= 4), go_rice is then the value carried from the position coded before; otherwise the
 // position is priced as bypass-coded and its Rice parameter comes from the levels decided around it.
@@ -1543,7 +1311,8 @@ template <typename DP> CTU_NOINLINE CTU_DEV rdoq_pos rdoq_decide(const rdoq_env 
 #if !defined(__HIPCC__)
 #include "ctu_rdoq_emul.h"
 #else
-// uvg_rdoq (rdo.c:1449-1870) by one wave: same arithmetic as rdoq_serial, restructured around what is sequential in it.
+// uvg_rdoq (rdo.c:1449-1870) by one wave: the arithmetic of the reference's walk (the host emulation's rdoq_serial, ctu_rdoq_emul.h),
+// restructured around what is sequential in it.
 //   * every position's quantisation candidate: all positions at once;
 //   * the positions of a 4x4 group are decided together by 16 lanes, up to four groups of one diagonal of the group grid at a time
 //     (a group per row of lanes: see the loop).  A decision reads only levels of positions later in scan
@@ -2618,36 +2387,6 @@ CTU_DEV int mb_load(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_ACQ
 CTU_DEV void mb_store(int32_t *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); }
 #endif
 
-#if !defined(CTU_PB) && !defined(__HIPCC__)
-// ---- the chroma helper (host emulation) ---------------------------------------------------------------------------------------
-// The fourth 4x4 CU of an 8x8 area carries the area's two 4x4 chroma blocks (search.c:355-400).  They depend on that CU's luma MODE
-// only, not on its luma block.  The device reconstructs the three blocks in one pass of the walk's wave (ctu_leaf4.h
-// leaf_recon_rows); the host emulation, which walks a 4x4 CU with the general evaluation, takes both orders: the Cb block on the
-// scratch of depth 3 ahead of the luma block, or all three in turn (g_emul_lazy).  Same arithmetic on the same inputs either way.
-template <typename PX> CTU_DEV void help_run(lds<PX> *S, const job<PX> &J)
-{
-  const int cx = S->help[0], cy = S->help[1], mode = S->help[2];
-  const int lx = cx & 63, ly = cy & 63;
-  PX *const ru = S->Du + ((ly >> 1) + 1) * PC + (lx >> 1) + 1;
-  int16_t *const ku = J.coeff + 4096 + (ly >> 1) * LCU_C + (lx >> 1);
-  const int has = recon_tu(S, J, 1, cx, cy, lx, ly, 8, mode, 0, ru, PC, ku, LCU_C, 8);
-  {
-    const int16_t *const from = wv_of(S)->lv1;          // the walk counts the levels' bits from ITS scratch
-    int16_t *const to = S->wv[0].lv1;
-    for (int e = 0; e < 16; ++e) to[e] = from[e];
-  }
-  S->help[3] = has;
-}
-template <typename PX> CTU_DEV bool help_post(lds<PX> *S, const job<PX> &J, int cx, int cy, int mode)
-{
-  if (g_emul_lazy) return false;                   // (the host tests take both roads)
-  S->help[0] = cx; S->help[1] = cy; S->help[2] = mode;
-  emul_on_wave(1, [&] { help_run(S, J); });
-  return true;
-}
-template <typename PX> CTU_DEV int help_wait(lds<PX> *S) { return S->help[3]; }
-#endif
-
 template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu(lds<PX> *S, const job<PX> &J, int L, int to_cand
 #if defined(CTU_PB)
                                                          , int forced_mode = -1      // P / B: the rough search already ran (ctu_pb.h); >= 0: its mode
@@ -2710,22 +2449,11 @@ template <typename PX> CTU_NOINLINE CTU_DEV void eval_cu(lds<PX> *S, const job<P
     rpy = PY; rpc = PC; kpy = LCU; kpc = LCU_C;
   }
   int cbf = 0;
-#if !defined(CTU_PB) && !defined(__HIPCC__)
-  const bool helped = sep && has_chroma && !to_cand && help_post(S, J, cx, cy, mode);
-#else
-  const bool helped = false;
-#endif
 #if defined(__HIPCC__)
 #pragma nounroll
 #endif
   for (int color = 0; color < (has_chroma ? 3 : 1); ++color) {
     const bool c = color != 0;
-#if !defined(CTU_PB) && !defined(__HIPCC__)
-    if (helped && color == 1) {
-      cbf |= help_wait(S) << 1;
-      continue;
-    }
-#endif
 #if defined(__HIPCC__) && !defined(CTU_PB)
     if (c && n == 8) {
       // the 4x4 chroma blocks of an 8x8 CU: the register-resident blocks of ctu_leaf4.h, Cb and Cr in one pass (the area's source
