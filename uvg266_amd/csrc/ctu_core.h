@@ -711,16 +711,98 @@ CTU_DEV unsigned satd4_tile(int (&d)[16])
   return (satd + 1) >> 1;
 }
 
+#if defined(__HIPCC__)
+// the sum of v over the wave's lanes (wave-uniform).  All 64 lanes must be active.
+CTU_DEV int rs_wave_sum(int v)
+{
+  v += dpp_xor1(v); v += dpp_xor2(v); v += dpp_mirror8(v); v += dpp_mirror16(v);          // every lane: the sum of its row of 16
+  return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48);
+}
+// rough_costs of a block of 8x8 or more on the device: 8x8 tiles, a lane per (mode, tile, row).  The angular modes of the list go
+// through ang_row8 (intra_pred_dev.h) -- the eight modes of a sweep of an 8x8 block share one straight line of code, their
+// parameters come from the leaf's LDS tables (lf_disp, lf_cubic), and whatever depends on the block's size alone is wave-uniform.
+// Planar and DC, round 0's first two entries, are a short sweep of their own on predict_row; only there is the DC value needed:
+// a sample per lane and a wave sum.  Sy: the block's source samples (pitch sps); modes: wctx::rs_list.
+template <typename PX> CTU_INLINE1 CTU_DEV void rough_costs8(lds<PX> *S, CTU_GLB const PX *Sy, int sps_, int n_, const int32_t *modes_, int n_modes_)
+{
+  wctx *const V = wv_of(S);
+  const int n = __builtin_amdgcn_readfirstlane(n_), n_modes = __builtin_amdgcn_readfirstlane(n_modes_), sps = __builtin_amdgcn_readfirstlane(sps_);
+  const int log2n = 31 - __builtin_clz((unsigned)n), lt = log2n - 3, lt2 = 2 * lt;      // 1 << lt tiles in a row, 1 << lt2 in the block
+  const int lane = CTU_TID, r = lane & 7, maxv = (int)px_info<PX>::maxv;
+  CTU_LDS const int32_t *const modes = LDSP(const int32_t, modes_);
+  CTU_LDS const uint32_t *const disp = LDSP(const uint32_t, S->lf_disp), *const cubic = LDSP(const uint32_t, S->lf_cubic);
+  const ref_rows_t<CTU_LDS const uint16_t *> R = {LDSP(const uint16_t, V->top), LDSP(const uint16_t, V->left), LDSP(const uint16_t, V->ftop), LDSP(const uint16_t, V->fleft)};
+  CTU_LDS uint32_t *const part = LDSP(uint32_t, V->part);
+  const int n_flat = __builtin_amdgcn_readfirstlane((n_modes > 0 && modes[0] < 2) + (n_modes > 1 && modes[1] < 2));
+  {
+    const int total = (n_modes - n_flat) << (lt2 + 3);
+    for (int base = 0; base < total; base += CTU_NT) {
+      const int idx = base + lane;
+      const bool on = idx < total;
+      const int task = (on ? idx >> 3 : 0) + (n_flat << lt2);
+      const int mi = task >> lt2, tile = task & ((1 << lt2) - 1), wy = (tile >> lt) * 8 + r, wx0 = (tile & ((1 << lt) - 1)) * 8;
+      const auto M = make_ang_mode(R, disp, modes[mi], log2n);
+      // the source samples of the work domain's row: a row of the block, or a column of it for the horizontal modes.  Every lane
+      // loads (a lane past the end has the first task's address), and all eight loads are out before the row is predicted
+      CTU_GLB const PX *const sp = Sy + (M.vertical ? wy * sps + wx0 : wx0 * sps + wy);
+      const int step = M.vertical ? 1 : sps;
+      int src[8], d[8], out[8], sad = 0;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) src[i] = (int)sp[i * step];
+      ang_row8(M, cubic, n, wy, wx0, maxv, out);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        d[i] = on ? src[i] - out[i] : 0;
+        sad += iabs_(d[i]);
+      }
+      const int satd = satd8_cost(d, r);
+      sad = dpp_group_sum<8>(sad);
+      if (on && r == 0) { part[2 * task] = (uint32_t)satd; part[2 * task + 1] = (uint32_t)sad; }
+    }
+  }
+  if (n_flat > 0) {
+    int acc = 0;                                // dc_value (intra.c:236-273) of a square block: top[1 .. n] + left[1 .. n]
+    for (int i = lane; i < 2 * n; i += CTU_NT) acc += (int)*(i < n ? R.top + 1 + i : R.left + 1 + i - n);
+    const int dcv = (rs_wave_sum(acc) + n) >> (log2n + 1);
+    const int total = n_flat << (lt2 + 3);
+    for (int base = 0; base < total; base += CTU_NT) {
+      const int idx = base + lane;
+      const bool on = idx < total;
+      const int task = on ? idx >> 3 : 0;
+      const int mi = task >> lt2, tile = task & ((1 << lt2) - 1), wy = (tile >> lt) * 8 + r, wx0 = (tile & ((1 << lt) - 1)) * 8;
+      const mode_info M = make_mode_info(modes[mi] != 0, n, n, 0);          // planar or DC
+      int src[8], d[8], out[8], sad = 0;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) src[i] = (int)Sy[wy * sps + wx0 + i];
+      predict_row<8>(M, R, dcv, 0, n, n, wy, wx0, maxv, out);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        d[i] = on ? src[i] - out[i] : 0;
+        sad += iabs_(d[i]);
+      }
+      const int satd = satd8_cost(d, r);
+      sad = dpp_group_sum<8>(sad);
+      if (on && r == 0) { part[2 * task] = (uint32_t)satd; part[2 * task + 1] = (uint32_t)sad; }
+    }
+  }
+  CTU_SYNC();
+}
+#endif
+
 // costs of the listed modes for the n x n luma block at (lx, ly); get_cost_dual (search_intra.c:133-192).
 // Device: every (mode, tile, row) is one lane -- a lane predicts one row of the tile in registers (in the mode's work domain:
 // transposed for the horizontal modes; SAD and the Hadamard magnitude multiset are transpose-invariant), the T lanes of a tile
-// finish the Hadamard with DPP exchanges (satd_dev.h).  Host emulation: the tile as a whole.
+// finish the Hadamard with DPP exchanges (satd_dev.h): rough_costs8 above, the loop below for a 4x4 block.  Host emulation: the
+// tile as a whole.
 template <typename PX> CTU_NOINLINE CTU_DEV void rough_costs(lds<PX> *S, const job<PX> &J, int lx, int ly, int n, const int32_t *modes, int n_modes)
 {
   wctx *const V = wv_of(S);
   int sps;
   CTU_GLB const PX *Sy = src_block(J, 0, lx, ly, &sps);
   const int T = n >= 8 ? 8 : 4, tiles_x = n / T, tiles = tiles_x * tiles_x;
+#if defined(__HIPCC__)
+  if (T == 8) { rough_costs8(S, Sy, sps, n, modes, n_modes); return; }      // (no DC value unless DC is listed)
+#endif
   const ref_rows_t<CTU_LDS const uint16_t *> R = {LDSP(const uint16_t, V->top), LDSP(const uint16_t, V->left), LDSP(const uint16_t, V->ftop), LDSP(const uint16_t, V->fleft)};
   const int dcv = dc_value(R.top, R.left, n, n);
   CTU_LDS uint32_t *const part = LDSP(uint32_t, V->part);
@@ -736,23 +818,10 @@ template <typename PX> CTU_NOINLINE CTU_DEV void rough_costs(lds<PX> *S, const j
     const bool on = idx < total;
     const int task0 = on ? idx / T : 0, r = idx & (T - 1);
     const int task = task0 + m_first * tiles;
-    const int mi = task / tiles, tile = task - mi * tiles;
+    const int mi = task / tiles;
     const mode_info M = make_mode_info(modes[mi], n, n, 0);
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
     int sad = 0, satd;
-    if (T == 8) {
-      int d[8], out[8];
-      predict_row<8>(M, R, dcv, 0, n, n, ty * 8 + r, tx * 8, (int)px_info<PX>::maxv, out);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int wx = tx * 8 + i, wy = ty * 8 + r;
-        const int bx = M.vertical ? wx : wy, by = M.vertical ? wy : wx;
-        d[i] = on ? (int)Sy[by * sps + bx] - out[i] : 0;
-        sad += iabs_(d[i]);
-      }
-      satd = satd8_cost(d, r);
-      sad = dpp_group_sum<8>(sad);
-    } else {
+    {
       int d[4], out[4];
       predict_row<4>(M, R, dcv, 0, n, n, r, 0, (int)px_info<PX>::maxv, out);
 #pragma unroll

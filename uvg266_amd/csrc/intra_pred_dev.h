@@ -223,3 +223,86 @@ __device__ __forceinline__ void predict_row(const mode_info &M, const RR &R, int
   }
 }
 
+// ---- the angular modes 2..66 of a SQUARE LUMA block of 8x8 or more, without a branch per mode kind (ctu_core.h rough_costs: the
+// lanes of a wave hold different modes, and every side of predict_row's branches would run for everybody) ----
+// What a lane needs to know about its mode: make_mode_info for w = h = n >= 8, luma.  A square block has no wide-angle mapping, so
+// |mode - 18| or |mode - 50| <= 16 is both the index of the angle tables and the distance that picks the filters.  `disp` is the
+// 17-entry table intraPredAngle | invAngle << 8 (on the device an LDS copy: lds::lf_disp); the PDPC scale comes from invAngle
+// itself (H.266 8.4.5.2.13: Min(2, Log2(n) - (Floor(Log2(3 * invAngle - 2)) - 8)), what kPreScale tabulates).
+template <typename RP> struct ang_mode {
+  RP mainr, side;       // the work domain's reference rows: the smoothed or the plain ones
+  int sd, inv;          // intraPredAngle, invAngle
+  int sc, lim;          // PDPC: its scale, and the columns x < lim it changes (0: the mode has none)
+  bool vertical, cubic; // mode >= 34: work domain == block domain, else transposed; the cubic taps, else the smoothing ones
+};
+template <typename RR, typename TP>
+__device__ __forceinline__ auto make_ang_mode(const RR &R, TP disp, int mode, int log2n) -> ang_mode<decltype(R.top)>
+{
+  ang_mode<decltype(R.top)> M;
+  const int thres = log2n <= 3 ? 14 : (log2n == 4 ? 2 : 0);      // kDistThres of 8x8, 16x16, 32x32 and larger
+  M.vertical = mode >= 34;
+  const int md = M.vertical ? mode - 50 : 18 - mode, amd = md < 0 ? -md : md;
+  const uint32_t t = disp[amd];
+  const int asd = (int)(t & 0xff);
+  M.inv = (int)(t >> 8);
+  M.sd = md < 0 ? -asd : asd;
+  const bool far = amd > thres, frac = (asd & 31) != 0;
+  const bool filtered = far && !frac;
+  M.cubic = !(far && frac);
+  const auto top = filtered ? R.ftop : R.top;
+  const auto left = filtered ? R.fleft : R.left;
+  M.mainr = M.vertical ? top : left;
+  M.side = M.vertical ? left : top;
+  // the pure modes (18, 50) always have their PDPC, the modes towards 2 and 66 where the scale is not negative, the others none
+  int sc = log2n - (23 - __clz(3 * M.inv - 2));
+  sc = sc > 2 ? 2 : sc;
+  sc = md == 0 ? (2 * log2n - 2) >> 2 : sc;
+  const bool pd = md >= 0 && sc >= 0;
+  M.sc = pd ? sc : 0;
+  M.lim = pd ? min(3 << M.sc, 1 << log2n) : 0;
+  return M;
+}
+// Row yd of the WORK domain, columns xd0 .. xd0 + 7: what predict_row<8> gives for the mode, as one straight line of code.  Every
+// mode goes through the four-tap sum: an integer slope (2, 34, 66) and the pure modes have phase 0 and the cubic taps {0, 64, 0, 0},
+// and (64 p + 32) >> 6 == p.  Both PDPC kinds are one predicated update (the angular one never leaves [0, maxv]: it moves a sample
+// towards a reference sample by at most half their difference, so the pure modes' clamp does nothing to it).  `cubic_tab`: kCubic,
+// 4 x int8 per phase in a word (lds::lf_cubic).  Reads the samples 0 .. 2 n + 2 of the main row: two beyond predict_row where the
+// phase is 0, times the taps that are 0.
+template <typename AM, typename TP>
+__device__ __forceinline__ void ang_row8(const AM &M, TP cubic_tab, int n, int yd, int xd0, int maxv, int (&out)[8])
+{
+  const int delta = M.sd * (yd + 1), di = delta >> 5, df = delta & 31;
+  int p[11];
+  int proj = 256 - (di + xd0) * M.inv;      // (-idx * inv + 256) of sample k: idx = di + xd0 + k
+#pragma unroll
+  for (int k = 0; k < 11; ++k) {
+    const int idx = di + xd0 + k;
+    const int s = min(proj >> 9, n);        // projected side reference (intra-generic.c:156-159)
+    const auto q = idx >= 0 ? M.mainr + idx : M.side + s;
+    p[k] = *q;
+    proj -= M.inv;
+  }
+  const int h = df >> 1;
+  // {16 - h, 32 - h, 16 + h, h} in the bytes of a word: no byte borrows (h <= 15)
+  const uint32_t fc = (uint32_t)cubic_tab[df];          // (read by every lane: a select, not a branch around the read)
+  const uint32_t f = M.cubic ? fc : 0x00102010u + (uint32_t)h * 0x0100FEFFu;
+  const int f0 = (int)(int8_t)(f & 0xff), f1 = (int)(int8_t)((f >> 8) & 0xff), f2 = (int)(int8_t)((f >> 16) & 0xff), f3 = (int)(int8_t)(f >> 24);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) out[i] = clampi((f0 * p[i] + f1 * p[i + 1] + f2 * p[i + 2] + f3 * p[i + 3] + 32) >> 6, 0, maxv);
+  if (xd0 < M.lim) {                        // (only the first tile or two of a row, and only half of the modes)
+    const int tl = M.mainr[0];
+    const bool pure = M.sd == 0;
+    int acc = 256 + (xd0 + 1) * M.inv;      // 256 + (x + 1) * inv
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int x = xd0 + i;
+      const bool in = x < M.lim;
+      const int l = M.side[in ? yd + (acc >> 9) + 1 : 0];       // (the pure modes: inv == 0, side[yd + 1])
+      const int wl = 32 >> ((2 * x) >> M.sc);
+      const int v = clampi(out[i] + ((wl * (l - (pure ? tl : out[i])) + 32) >> 6), 0, maxv);
+      out[i] = in ? v : out[i];
+      acc += M.inv;
+    }
+  }
+}
+
