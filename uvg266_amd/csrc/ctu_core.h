@@ -1300,6 +1300,72 @@ CTU_DEV uint32_t coded_level(const rdoq_env &E, double *coded_cost, double coded
   return best;
 }
 
+// coded_level as straight-line code: what every lane of a wave runs when the lanes hold different levels (the device's call sites;
+// the host emulation's rdoq_serial keeps coded_level, and tests/test_rdoq_level_decision.py holds the two together bit for bit).
+//   * the two bin costs of a model lie side by side in tab_rdoq_bits(): the pairs of the significance, parity, greater-1 and
+//     greater-2 models are read once, in front of everything, and serve both candidates and "not significant";
+//   * both candidates -- a1 = max_abs_level, a2 = max_abs_level - 1, each >= 1 -- are priced, and a predicate says which count;
+//   * the rate's terms are integers (their order is free); the doubles are the reference's, in the reference's order.
+// The escape code of uvg_get_ic_rate (Golomb-Rice up to 5 << rice, then exp-Golomb with the prefix capped at 12) without its loop:
+// the prefix is floor(log2(suffix + 1)).
+CTU_DEV int32_t rq_escape_rate(int32_t symbol, int go_rice)
+{
+  const int32_t q = symbol >> go_rice;
+  const bool rice_code = q < 5;
+  const uint32_t arg = rice_code ? 1u : (uint32_t)(q - 4);          // (never 0: clz(0) is undefined)
+  const int32_t log2 = 31 - (int32_t)__builtin_clz(arg);
+  const int32_t prefix = log2 < 12 ? log2 : 12;
+  const int32_t suffix_len = prefix == 12 ? 15 - go_rice : prefix + 1;
+  return (rice_code ? q + 1 + go_rice : 5 + prefix + suffix_len + go_rice) << 15;
+}
+struct rq_pair { int32_t b0, b1; };
+CTU_DEV rq_pair rbits2(int model)
+{
+  CTU_LDS const uint32_t *const p = LDSP(const uint32_t, tab_rdoq_bits()) + 2 * model;
+  rq_pair r;
+  r.b0 = (int32_t)p[0]; r.b1 = (int32_t)p[1];
+  return r;
+}
+// uvg_get_ic_rate (limited prefix length) of a level a >= 1
+CTU_DEV int32_t rq_level_rate(int32_t a, bool regular, int go_rice, rq_pair par, rq_pair gt1, rq_pair gt2)
+{
+  // regular: greater-1; from 2 on parity and greater-2; from 4 on the escape code of a - 4.  Bypass: the escape code of the level
+  // itself, with the levels up to 1 << rice moved down by one (level 0 has their place)
+  const int32_t s_reg = a - 4, s_byp = a <= (1 << go_rice) ? a - 1 : a;
+  const int32_t s = regular ? (s_reg > 0 ? s_reg : 0) : s_byp;
+  const int32_t esc = rq_escape_rate(s, go_rice);
+  const int32_t flags = (a >= 2 ? gt1.b1 + ((a & 1) ? par.b1 : par.b0) + (a >= 4 ? gt2.b1 : gt2.b0) : gt1.b0) + (a >= 4 ? esc : 0);
+  return (1 << 15) + (regular ? flags : esc);
+}
+CTU_DEV uint32_t coded_level2(const rdoq_env &E, double *coded_cost, double coded_cost0, double *coded_cost_sig, int32_t level_double,
+                              uint32_t max_abs_level, int ctx_sig, int ctx_set, int go_rice, uint32_t reg_bins, int last)
+{
+  const int tofs = E.t ? 21 : 0;
+  const rq_pair sig = rbits2(M_SIG + (E.t ? 12 : 0) + ctx_sig), par = rbits2(M_PAR + tofs + ctx_set), gt1 = rbits2(M_GT1 + tofs + ctx_set),
+                gt2 = rbits2(M_GT2 + tofs + ctx_set);
+  const bool regular = reg_bins >= 4;
+  const int32_t mal = (int32_t)max_abs_level;
+  const int32_t a1 = mal > 1 ? mal : 1, a2 = mal > 2 ? mal - 1 : 1;
+  const int32_t rate1 = rq_level_rate(a1, regular, go_rice, par, gt1, gt2), rate2 = rq_level_rate(a2, regular, go_rice, par, gt1, gt2);
+  // "not significant" where the reference allows it
+  const bool zero_ok = !last && mal < 3;
+  const double sig0 = E.lambda * sig.b0;
+  const double cur_cost_sig = last ? 0.0 : E.lambda * sig.b1;
+  double cost = zero_ok ? coded_cost0 + sig0 : 1.7e+308, cost_sig = zero_ok ? sig0 : *coded_cost_sig;
+  uint32_t best = 0;
+  const double err1 = (double)(level_double - (a1 * (1 << E.q_bits))), err2 = (double)(level_double - (a2 * (1 << E.q_bits)));
+  double cur1 = err1 * err1 * E.error_scale + E.lambda * rate1, cur2 = err2 * err2 * E.error_scale + E.lambda * rate2;
+  cur1 += cur_cost_sig;
+  cur2 += cur_cost_sig;
+  const bool take1 = mal >= 1 && cur1 < cost;
+  best = take1 ? (uint32_t)a1 : best; cost = take1 ? cur1 : cost; cost_sig = take1 ? cur_cost_sig : cost_sig;
+  const bool take2 = mal >= 2 && cur2 < cost;
+  best = take2 ? (uint32_t)a2 : best; cost = take2 ? cur2 : cost; cost_sig = take2 ? cur_cost_sig : cost_sig;
+  *coded_cost = cost;
+  *coded_cost_sig = cost_sig;
+  return best;
+}
+
 // context_get_sig_ctx_idx_abs / templateAbsSum on a level array (rdo.c:1400-1438, 846-871), no MTS zero-out
 template <typename LP> CTU_DEV int sig_ctx_abs(LP lv, int px, int py, int n, int color, int *diag_out, int *sum_out)
 {
@@ -1349,6 +1415,34 @@ __device__ static const double kPow2[16] = {1.0, 2.0, 4.0, 8.0, 16.0, 32.0, 64.0
 // regular: regular bins remain (reg_bins >= 4), go_rice is then the value carried from the position coded before; otherwise the
 // position is priced as bypass-coded and its Rice parameter comes from the levels decided around it.
 struct rdoq_pos { int level; double cc, cs; };
+// ... of a position whose candidate is known (level_double, max_abs_level): what a round of rdoq_wave's fixed point repeats.  The five
+// levels of the context template (context_get_sig_ctx_idx_abs and template_abs_sum(dst, 0, ...) read the same ones: sig_ctx_abs,
+// template_abs_sum above) are fetched in one batch, each from its own address where the block has it and from the position itself
+// otherwise, and the block's edges mask the VALUES: no read waits behind a branch.  (The int16_t accumulator's wrap, rdo.c:849, is
+// the wrap of the whole sum.)
+template <typename DP> CTU_INLINE CTU_DEV rdoq_pos rdoq_decide_at(const rdoq_env &E, DP dst, int n, int color, int pos_x, int pos_y, bool is_last, bool regular, int go_rice,
+                             double c0, int32_t level_double, uint32_t max_abs_level)
+{
+  const bool x1 = pos_x < n - 1, x2 = pos_x < n - 2, y1 = pos_y < n - 1, y2 = pos_y < n - 2;
+  const auto d = dst + pos_x + pos_y * n;
+  const int v1 = d[x1 ? 1 : 0], v2 = d[x2 ? 2 : 0], v5 = d[x1 && y1 ? n + 1 : 0], v4 = d[y1 ? n : 0], v8 = d[y2 ? n << 1 : 0];
+  int num_pos = 0, sum_abs = 0, sum_lev = 0;
+#define CTU_UPD(v, on) { const int a = (on) ? iabs_((int)(v)) : 0; sum_abs += (4 + (a & 1)) < a ? (4 + (a & 1)) : a; num_pos += a ? 1 : 0; sum_lev += a; }
+  CTU_UPD(v1, x1) CTU_UPD(v2, x2) CTU_UPD(v5, x1 && y1) CTU_UPD(v4, y1) CTU_UPD(v8, y2)
+#undef CTU_UPD
+  const int diag = pos_x + pos_y, tsum = sum_abs - num_pos;
+  int ctx_sig = (((sum_abs + 1) >> 1) < 3 ? ((sum_abs + 1) >> 1) : 3) + (diag < 2 ? 4 : 0);
+  if (color == 0) ctx_sig += diag < 5 ? 4 : 0;
+  int ctx_set = ((tsum < 4 ? tsum : 4) + 1) + (!diag ? ((color == 0) ? 15 : 5) : (color == 0) ? (diag < 3 ? 10 : (diag < 10 ? 5 : 0)) : 0);
+  ctx_sig = is_last ? 0 : ctx_sig;
+  ctx_set = is_last ? 0 : ctx_set;
+  const int t16 = (int)(int16_t)sum_lev, tcap = t16 < 31 ? t16 : 31;
+  go_rice = regular ? go_rice : go_rice_par((unsigned)(tcap > 0 ? tcap : 0));          // template_abs_sum(dst, 0, ...)
+  rdoq_pos r;
+  r.cs = 0;        // (the reference leaves cost_sig of the last position as it was: never read before it is written, see below)
+  r.level = (int)coded_level2(E, &r.cc, c0, &r.cs, level_double, max_abs_level, ctx_sig, ctx_set, go_rice, regular ? 4u : 0u, is_last);
+  return r;
+}
 template <typename DP> CTU_INLINE CTU_DEV rdoq_pos rdoq_decide_inl(const rdoq_env &E, CTU_LDS const int16_t *coef, DP dst, int n, int l2, int color, int blkpos, bool is_last,
                              bool regular, int go_rice, double c0, int *mal_out)
 {
@@ -1358,18 +1452,8 @@ template <typename DP> CTU_INLINE CTU_DEV rdoq_pos rdoq_decide_inl(const rdoq_en
   const int32_t level_double = (int32_t)(prod < cap ? prod : cap);
   const uint32_t max_abs_level = (uint32_t)(level_double + cap_half) >> E.q_bits;
   const int pos_y = blkpos >> l2, pos_x = blkpos - (pos_y << l2);
-  int ctx_sig = 0, ctx_set = 0;
-  if (!is_last) {
-    int diag, tsum;
-    ctx_sig = sig_ctx_abs(dst, pos_x, pos_y, n, color, &diag, &tsum);
-    ctx_set = ((tsum < 4 ? tsum : 4) + 1) + (!diag ? ((color == 0) ? 15 : 5) : (color == 0) ? (diag < 3 ? 10 : (diag < 10 ? 5 : 0)) : 0);
-  }
-  if (!regular) go_rice = go_rice_par(template_abs_sum(dst, 0, pos_x, pos_y, n));
-  rdoq_pos r;
-  r.cs = 0;        // (the reference leaves cost_sig of the last position as it was: never read before it is written, see below)
-  r.level = (int)coded_level(E, &r.cc, c0, &r.cs, level_double, max_abs_level, ctx_sig, ctx_set, go_rice, regular ? 4u : 0u, is_last);
   *mal_out = (int)max_abs_level;
-  return r;
+  return rdoq_decide_at(E, dst, n, color, pos_x, pos_y, is_last, regular, go_rice, c0, level_double, max_abs_level);
 }
 template <typename DP> CTU_NOINLINE CTU_DEV rdoq_pos rdoq_decide(const rdoq_env &E, CTU_LDS const int16_t *coef, DP dst, int n, int l2, int color, int blkpos, bool is_last,
                              bool regular, int go_rice, double c0, int *mal_out)
@@ -1535,6 +1619,8 @@ template <typename PX> CTU_INLINE1 CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W
           bool changed = false;
           RQ_N(12, 1)
           if (mine) {
+            // (the candidate is the pass's level_double / mal1 again; handing those in instead keeps four more registers alive across
+            // the loop and costs the 10-bit kernels 16 B of stack per lane, over the ceilings of tests/test_abi.py)
             int mal;
             const rdoq_pos r = rdoq_decide_inl(E, coef, dst, n, l2, color, blk, is_last, regular != 0, go_rice, c0, &mal);
             cc = r.cc; cs = r.cs;

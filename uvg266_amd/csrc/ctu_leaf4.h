@@ -735,7 +735,7 @@ template <typename PX> CTU_DEV int leaf_rdoq(lds<PX> *S, int coef, int color, in
       int go_rice = go_rice_reg;
       if (!regular) { const int v = tsum_lev < 31 ? tsum_lev : 31; go_rice = go_rice_par((unsigned)v); }      // template_abs_sum(dst, 0, ...)
       cs = 0;
-      level = (int)coded_level(E, &cc, c0, &cs, level_double, (uint32_t)mal, ctx_sig, ctx_set, go_rice, regular ? 4u : 0u, is_last);
+      level = (int)coded_level2(E, &cc, c0, &cs, level_double, (uint32_t)mal, ctx_sig, ctx_set, go_rice, regular ? 4u : 0u, is_last);
     }
     const bool changed = mine && level != lev;
     lev = level;
@@ -934,7 +934,7 @@ template <typename PX> CTU_DEV int leaf_rdoq_rows(lds<PX> *S, int coef, int colo
       int go_rice = go_rice_reg;
       if (!regular) { const int v = tsum_lev < 31 ? tsum_lev : 31; go_rice = go_rice_par((unsigned)v); }      // template_abs_sum(dst, 0, ...)
       cs = 0;
-      level = (int)coded_level(E, &cc, c0, &cs, level_double, (uint32_t)mal, ctx_sig, ctx_set, go_rice, regular ? 4u : 0u, is_last);
+      level = (int)coded_level2(E, &cc, c0, &cs, level_double, (uint32_t)mal, ctx_sig, ctx_set, go_rice, regular ? 4u : 0u, is_last);
     }
     const bool changed = mine && level != lev;
     lev = level;
