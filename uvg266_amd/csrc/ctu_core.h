@@ -1461,6 +1461,16 @@ template <typename DP> CTU_NOINLINE CTU_DEV rdoq_pos rdoq_decide(const rdoq_env 
   return rdoq_decide_inl(E, coef, dst, n, l2, color, blkpos, is_last, regular, go_rice, c0, mal_out);
 }
 
+// the last-position search's choice among the sixteen totals of a group (rdo.c:1805-1825).  The reference walks the positions in
+// descending scan order and takes a candidate's total when it is strictly below the best cost so far: the lowest total wins, among
+// equal totals the first met -- the highest k -- and a total equal to the incoming best_cost loses to it.  That is a reduction whose
+// result does not depend on its order: the lower of two totals (rq_last_lower; a lane that is no candidate enters best_cost, which
+// can only tie), then the highest candidate at the minimum, if the minimum is below best_cost at all (rq_last_pick).  Plain C++:
+// rdoq_wave runs both on the lanes' registers, tests/emul_rdoq/last_pick.cpp on the host against the walk.
+CTU_DEV double rq_last_lower(double a, double b) { return b < a ? b : a; }
+// at_min: the candidates whose total equals the minimum m (bit k: position k of the group).  -> k + 1 of the winner, 0: best_cost stays
+CTU_DEV int rq_last_pick(double m, unsigned at_min, double best_cost) { return (m < best_cost && at_min) ? 32 - __builtin_clz(at_min) : 0; }
+
 #if !defined(__HIPCC__)
 #include "ctu_rdoq_emul.h"
 #else
@@ -1476,11 +1486,19 @@ template <typename DP> CTU_NOINLINE CTU_DEV rdoq_pos rdoq_decide(const rdoq_env 
 //     out for good; the one or two groups where it does run out are walked position by position by lane 0;
 //   * the double-precision sums the reference forms in scan order (base cost, group statistics, the last-position search): every
 //     lane forms them, in the reference's order, from the owners' registers (v_readlane at fixed lanes, sixteen unrolled steps per
-//     group; predicates applied by the owners, integers from ballots) -- no memory and no branch in the chain.
+//     group; predicates applied by the owners, integers from ballots) -- no memory and no branch in the chain.  The last-position
+//     search keeps one chain only, base_cost, and that one runs down the owners' lanes (a wave shift a step); the sixteen totals
+//     are formed once, each in its lane, and the choice among them is a reduction (rq_last_lower, rq_last_pick) -- in the intra
+//     kernel; with CTU_PB that search is still every lane's uniform chain (see there).
 // Result: V->rq_i[1] = whether any level survived; levels in dst.
 CTU_DEV double rl64(double v, int lane)
 {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+  return __hiloint2double(hi, lo);
+}
+template <int CTRL> CTU_DEV double dpp64(double v)          // both halves through one DPP control; a lane without a source reads +0.0
+{
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true), hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
   return __hiloint2double(hi, lo);
 }
 CTU_DEV double shfl64(double v, int from)
@@ -1795,10 +1813,18 @@ template <typename PX> CTU_INLINE1 CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W
     // of equal totals in descending order wins; then its level's cost leaves base_cost and its level-0 cost comes back, while a
     // zero's significance flag leaves it (and +0.0 comes back: k0 is zero there).  The walk ends at the first level above 1: known
     // from a ballot, the positions below it are no candidates and base_cost is not read again.
+    // Only base_cost is a chain here, and every step of it is in its owner's registers: lane k holds base_cost as its own step
+    // leaves it (after), formed from what lane k + 1 left (before).  A round takes the neighbour's value down one lane and redoes
+    // the step; lane 15's is right from the start, lane k's after 15 - k rounds, and a round more changes nothing.  The lanes above
+    // 15 hold no position (kx and k0 are +0.0 there: base_cost passes through them as it came), so the shift runs over the whole
+    // wave and lane 15 reads the incoming base_cost from lane 16; what enters at lane 63 gets as far as lane 49.
     const double kx = klev ? kcc : kcs;
     const unsigned m_nz = (unsigned)__ballot(klev != 0), m_gt1 = (unsigned)__ballot(klev > 1);
     const int kstop = m_gt1 ? 31 - __clz(m_gt1) : 0;
     const unsigned cand = m_nz >> kstop << kstop;
+#if defined(CTU_PB)
+    // The P / B kernel keeps the walk as every lane's uniform chain on v_readlane: built with the lanes' form below, its test met
+    // an illegal memory access on the device whose cause was not found (profiles/README.md, tag r17).
     if (cgs < cg_last || (last_scanpos & 15) >= 8) {              // (wave-uniform, as is kstop < 8 below)
 #pragma unroll
       for (int k = 15; k >= 8; --k) {
@@ -1819,6 +1845,25 @@ template <typename PX> CTU_INLINE1 CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W
         base_cost = base_cost - rl64(kx, k) + rl64(k0, k);
       }
     }
+#else
+    double before = base_cost, after = base_cost - kx + k0;
+#pragma unroll
+    for (int i = 0; i < 15; ++i) {
+      before = dpp64<0x130>(after);                                 // wave_shl:1
+      after = before - kx + k0;
+    }
+    // the sixteen totals in their lanes, the choice among them: rq_last_lower / rq_last_pick above
+    const double total = before + klast - kcs;
+    const bool is_cand = own && (cand >> sp & 1u) != 0;
+    double m = is_cand ? total : best_cost;
+    m = rq_last_lower(m, dpp64<0xB1>(m));                           // quad_perm [1,0,3,2]
+    m = rq_last_lower(m, dpp64<0x4E>(m));                           // quad_perm [2,3,0,1]
+    m = rq_last_lower(m, dpp64<0x141>(m));                          // row_half_mirror
+    m = rq_last_lower(m, dpp64<0x140>(m));                          // row_mirror: every lane of the row has the row's minimum
+    const int pick = rq_last_pick(rl64(m, 0), (unsigned)__ballot(is_cand && total == m), best_cost);
+    if (pick) { best_last_idx_p1 = cgs * 16 + pick; best_cost = rl64(m, 0); }
+    base_cost = rl64(after, 0);                                     // (after step 0: read again only when no level above 1 was met)
+#endif
     found_last = m_gt1 != 0;
   }
   if (CTU_TID == 0) V->rq_i[1] = best_last_idx_p1 > 0;
