@@ -1069,8 +1069,15 @@ typedef struct uvghip_slice_pb_t {
   const int32_t *col;              /* DEVICE: the collocated picture ref_LX[0][0] on its 8x8 grid (uvghip_merge_cand_batch's layout) */
   const uvghip_inter4_t *inter4;   /* DEVICE, cu_stride entries per row */
   const uint32_t *models_inter;    /* DEVICE: per CTU three sets of the 18 inter-syntax models (state0 | state1 << 16), as `models` holds the 257 */
-  int32_t col_stride, reserved;    /* > 0: `col` is the collocated picture's per-4x4 motion table (uvghip_ctu_pb_picture_t.motion_out) with this many
+  int32_t col_stride;              /* > 0: `col` is the collocated picture's per-4x4 motion table (uvghip_ctu_pb_picture_t.motion_out) with this many
                                     * units per row, read at its even positions; 0: `col` is already the 8x8 grid */
+  int32_t second_pass;             /* uvghip_encode_slice_rows_pb_alf only (the plain entry point ignores it), != 0: the rows are the SECOND coding
+                                    * pass of the picture, as in every --alf run of the encoder -- it codes the CTUs once behind their search to keep
+                                    * its models going and for real after the picture's ALF (src/encoderstate.c:856-860, 1043-1052), and clears a
+                                    * row's history table (HMVP) before the first pass only (:1021-1028).  The AMVP predictors of the bitstream's
+                                    * pass are derived with the table the row's first pass left, so its mvd bins, and the models a row hands to
+                                    * the row below, are not those of the first pass (which `models` / `models_inter` hold): every row derives
+                                    * its start by coding, into nothing, the first CTU of each row above.  0: one pass, the table starts empty */
 } uvghip_slice_pb_t;
 /* uvghip_encode_slice_rows for P / B pictures: the skip flag, prediction mode, merge flag / index, inter direction, reference indices,
  * motion vector differences against the AMVP predictor the CU chose (uvg_inter_get_mv_cand_cua on the picture's side information with the
@@ -1099,6 +1106,16 @@ UVGHIP_API size_t uvghip_slice_rows_alf_workspace_bytes(int n_pictures);
 UVGHIP_API int uvghip_encode_slice_rows_alf(int bitdepth, const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, const uvghip_slice_alf_t *alf,
                                             int n_pictures, const int32_t *sao_info, const uint16_t *sao_models, void *workspace, uint8_t *out, int row_cap,
                                             int32_t *row_bytes, void *stream);
+
+/* uvghip_encode_slice_rows_pb for P / B pictures of an --alf on / --alf full run: both tables -- pb[n_pictures] and alf[n_pictures], HOST
+ * arrays as in the two entry points above, uploaded in stream order -- and the CTU-level ALF syntax between a CTU's SAO syntax and its
+ * coding tree, its models initialised for the slice type.  A picture whose enabled[] and cc_enabled[] are all zero codes no ALF bin: with
+ * pb[i].second_pass == 0 its rows are uvghip_encode_slice_rows_pb's.  A picture of a real --alf run has second_pass = 1, ALF on or off in its
+ * slice (uvghip_loop_pb_alf_stage sets it).  workspace: uvghip_slice_rows_pb_alf_workspace_bytes(n_pictures). */
+UVGHIP_API size_t uvghip_slice_rows_pb_alf_workspace_bytes(int n_pictures);
+UVGHIP_API int uvghip_encode_slice_rows_pb_alf(int bitdepth, const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, const uvghip_slice_pb_t *pb,
+                                               const uvghip_slice_alf_t *alf, int n_pictures, const int32_t *sao_info, const uint16_t *sao_models, void *workspace,
+                                               uint8_t *out, int row_cap, int32_t *row_bytes, void *stream);
 
 /* The ALF stage of a picture group behind uvghip_loop_plan_run (BASELINE configs[3]: --alf full) -- where the encoder runs
  * uvg_alf_enc_process (src/alf.c:5193) on pictures whose search, deblocking and SAO the device did.  The derivation of the decisions
@@ -1208,6 +1225,20 @@ typedef struct uvghip_alf_aps {
 } uvghip_alf_aps_t;
 UVGHIP_API int uvghip_write_idr_nals_alf(int poc, int qp_delta, int sao, const uvghip_alf_slice_t *alf, const uvghip_alf_aps_t *aps, int n_aps, const uint8_t *rows,
                                          size_t row_pitch, const int32_t *row_bytes, int n_rows, const uint32_t *checksum, uint8_t *out, size_t cap, size_t *len);
+
+/* ... of a picture of an --alf on / --alf full stream WITH a GOP structure (BASELINE configs[3]: --gop 16): uvghip_write_picture_nals_gop
+ * plus the APS NAL units in front of the slice and the slice header's ALF fields, which stand behind sh_slice_type /
+ * sh_no_output_of_prior_pics_flag and in front of the reference picture lists (src/encoder_state-bitstream.c:1283-1330).  The first NAL unit
+ * of the access unit -- the first APS, or the slice when n_aps == 0 -- takes the long start code.  alf is required (the SPS of such a stream
+ * has ALF on: a slice with everything off still carries slice_alf_enabled_flag = 0).
+ * nal_type: 0 TRAIL, 3 RASL, 9 CRA as uvghip_write_picture_nals_gop, and 7 / 8 (IDR_W_RADL / IDR_N_LP: slice_type 2, no reference lists, the
+ * POC in poc_lsb_bits bits; an IDR picture with poc 0 follows the stream's parameter sets and takes short start codes as in
+ * uvghip_write_idr_nals_alf).  copy_rpl1: as in uvghip_write_picture_nals_pb (a low-delay structure with cfg.bipred: list 1 signalled as a
+ * copy of list 0's entries, n_ref_pos = 0); 0 for a random-access stream.  HOST function. */
+UVGHIP_API int uvghip_write_picture_nals_gop_alf(int nal_type, int poc, int poc_lsb_bits, int slice_type, int n_ref_neg, const int32_t *delta_neg, int n_ref_pos,
+                                                 const int32_t *delta_pos, int copy_rpl1, int tmvp, int qp_delta, int sao, const uvghip_alf_slice_t *alf,
+                                                 const uvghip_alf_aps_t *aps, int n_aps, const uint8_t *rows, size_t row_pitch, const int32_t *row_bytes, int n_rows,
+                                                 const uint32_t *checksum, uint8_t *out, size_t cap, size_t *len);
 
 /* After uvghip_loop_plan_run: the NAL units (slice + hash SEI) of picture `picture` of the plan's group as picture number `poc` of the
  * stream, into HOST memory -- uvghip_picture_checksum on its output picture, its rows brought to the host, uvghip_write_picture_nals.
@@ -1456,6 +1487,22 @@ UVGHIP_API size_t uvghip_loop_pb_workspace_bytes(int bitdepth, int n_pictures, i
 UVGHIP_API int uvghip_loop_pb_run(int bitdepth, const uvghip_loop_pb_picture_t *pictures, int n_pictures, int sao_type, void *workspace, void *stream);
 UVGHIP_API int uvghip_loop_pb_results(int bitdepth, int n_pictures, int pic_w, int pic_h, void *workspace, const int32_t **sao_info,
                                       const uint16_t **sao_models, const uint8_t **rows, const int32_t **row_bytes, int *row_cap, int *n_rows);
+
+/* The ALF stage behind uvghip_loop_pb_run, on the same pictures[] and loop workspace (what uvghip_loop_plan_alf_stage is behind
+ * uvghip_loop_plan_run): per picture `decide` -- the same callback type, handed a uvghip_loop_picture_t view of search.pic and out_* (the
+ * picture ALF gets = the loop's SAO output) -- then uvghip_alf_reconstruct_picture from out_* into alf_out[i] (a picture with nothing enabled
+ * is copied), and per run of pictures with equal QP, lambda and slice type (the runs of uvghip_loop_pb_run)
+ * uvghip_encode_slice_rows_pb_alf with the loop's SAO decisions: rows / row_bytes ([picture][row][row_cap] bytes, [picture][row] lengths;
+ * device memory) replace the rows uvghip_loop_pb_run coded, which carry no ALF syntax.  sao_type, classification_shift: as in
+ * uvghip_loop_pb_run / uvghip_loop_plan_alf_stage.  workspace: uvghip_loop_pb_alf_workspace_bytes of device memory.
+ * alf_out[i] is the picture the encoder returns, hashes AND predicts from: pictures that reference picture i must be given alf_out[i] as
+ * ref_y / ref_u / ref_v, not out_*.  So the stage of a picture runs before any picture that references it is issued; the derivation needs the
+ * whole picture's statistics, which is why the in-flight entry points below take no ALF argument.
+ * The call returns with the stream's work enqueued; it synchronises the stream between pictures (the decisions are host data). */
+UVGHIP_API size_t uvghip_loop_pb_alf_workspace_bytes(int bitdepth, int n_pictures, int pic_w, int pic_h);
+UVGHIP_API int uvghip_loop_pb_alf_stage(int bitdepth, const uvghip_loop_pb_picture_t *pictures, int n_pictures, int sao_type, void *loop_workspace,
+                                        uvghip_alf_decide_fn decide, void *user, int classification_shift, const uvghip_alf_planes_t *alf_out, void *workspace,
+                                        uint8_t *rows, int row_cap, int32_t *row_bytes, void *stream);
 
 /* uvghip_loop_pb_run for pictures IN FLIGHT behind their references -- the encoder's --owf schedule (src/encoderstate.c:1060-1116: with
  * cfg.owf != 0 the search of CTU (x, y) of a picture waits for CTU (x + 2, y + 1) of its reference, clamped to the picture;

@@ -315,12 +315,21 @@ def moving_picture(W, H, t, depth):
     return helpers.moving_picture(W, H, t, depth)
 
 
-def inter(W, H, depth, qp, frames, extra=(), suffix="", with_levels=True, out_dir=None, clip=False):
+def inter(W, H, depth, qp, frames, extra=(), suffix="", with_levels=True, out_dir=None, clip=False, alf=False):
     """Inter encode -- low delay (--gop lp-g4d3t1, BASELINE configs[2]) unless `extra` names another GOP ("gop", "16": the random-access
     structure --preset medium / slow run with by default): per picture the reference lists and the picture after the in-loop
     filters, per CTU the side information incl. motion, the levels and the reconstruction before the filters -- what a reconstruction
     of the encoder's decisions (motion compensation + residual) needs.  Every per-picture array is in CODING order; `display[f]` is the
-    display index (= the source picture) of coded picture f.  clip: sources from helpers.clip_picture (any length) instead of moving_picture."""
+    display index (= the source picture) of coded picture f.  clip: sources from helpers.clip_picture (any length) instead of moving_picture.
+    alf: the run has --alf full on (one worker thread, no frames in flight: see full()).  Every CTU is then coded twice -- simulated during the
+    search, for real after uvg_alf_enc_process (encoderstate.c:1040-1052) --, and the "coded" / "row" items kept are the second pass: the
+    bitstream.  Per coded picture the file also holds the decisions ALF took and the picture it received (record "alf": alf_meta, alf_flags,
+    alf_set_idx, alf_luma_aps, alf_chroma_aps, alf_cc_coeff, alf_pre_y / u / v) and, in the order they were written, the APS NAL units
+    (record "aps": aps_meta -- [0] = the coded picture they precede --, aps_luma, aps_chroma, aps_cc), named as stream_alf() names them.
+    `final_*` is then the picture ALF left."""
+    if alf:
+        extra = tuple(extra) + ("alf", "full", "threads", "1", "owf", "0")
+        suffix += "_alf"
     if clip:          # True / 1: helpers.clip_picture; 2: helpers.plateau_picture (helpers.CLIP_GENERATORS)
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import helpers
@@ -360,6 +369,16 @@ def inter(W, H, depth, qp, frames, extra=(), suffix="", with_levels=True, out_di
     models = np.zeros((n, 3, 1286), np.uint8)            # at the CTU's start / after its search / after the coder (257 models: state0, state1, rate)
     models_inter = np.zeros((n, 3, 90), np.uint8)        # the 18 models of the inter syntax beside them
     sao_models = np.zeros((n, 6), np.uint16)             # the two SAO models after the CTU's SAO syntax
+    if alf:
+        # per picture the rows of the simulated pass, then those of the real one (one worker thread: picture after picture)
+        assert len(ROWS) == 2 * frames * hc and len([1 for nm, r in recs if nm == "coded"]) == 2 * len(S)
+        assert [int(r[0][0]) for r in ROWS] == list(range(hc)) * (2 * frames)
+        ROWS = [r for k, r in enumerate(ROWS) if (k // hc) & 1]
+        at, bs = 0, open(out + ".266", "rb").read()
+        for r in ROWS:          # ... which are the bitstream's, in this order
+            at2 = bs.find(r[1].tobytes(), at)
+            assert at2 >= 0, "a row of the second pass is not in the .266"
+            at = at2 + len(r[1])
     assert len(ROWS) == frames * hc
     row_off = np.concatenate([[0], np.cumsum([len(r[1]) for r in ROWS])]).astype(np.int64).reshape(-1)
     row_bytes = np.concatenate([r[1] for r in ROWS])     # every WPP row's substream (emulation prevention included), pictures in coding order
@@ -389,8 +408,23 @@ def inter(W, H, depth, qp, frames, extra=(), suffix="", with_levels=True, out_di
     assert sorted(display.tolist()) == list(range(frames)), display
     final = [np.stack([F[display[f]][1 + c].reshape(H >> (c > 0), W >> (c > 0)) for f in range(frames)]) for c in range(3)]
     src_crc = np.array([zlib.crc32(b"".join(p.tobytes() for p in moving_picture(W, H, t, depth))) for t in range(frames)], np.uint32)
-    np.savez_compressed(os.path.join(out_dir or os.path.join(ROOT, "tests/golden"), f"ref_inter_{tag}.npz"), dims=np.array([W, H, depth, qp, frames], np.int32), meta=meta, cu=cu, lam=lam, sao=sao, src_crc=src_crc,
-                        motion=mot, refs=refs, rec_y=rec[0], rec_u=rec[1], rec_v=rec[2], coeff=coeff if with_levels else coeff[:0], final_y=final[0], final_u=final[1],
+    more, keep_rec = {}, None
+    if alf:
+        keep_rec = 0          # (the reconstruction before the filters stays out: alf_pre_* and final_* are what these files are for, and each stays below 1 MB)
+        A = sorted([r for nm, r in recs if nm == "alf"], key=lambda r: int(r[0][0]))
+        P = [r for nm, r in recs if nm == "aps"]
+        assert [int(a[0][0]) for a in A] == list(range(frames)) and all(0 <= int(r[0][0]) < frames for r in P)
+        assert [int(r[0][0]) for r in P] == sorted(int(r[0][0]) for r in P)
+        more = dict(alf_meta=np.stack([a[0] for a in A]), alf_flags=np.stack([a[7].reshape(7, wc * hc) for a in A]), alf_set_idx=np.stack([a[8] for a in A]),
+                    alf_luma_aps=np.stack([a[9].reshape(8, -1) for a in A]), alf_chroma_aps=np.stack([a[10] for a in A]), alf_cc_coeff=np.stack([a[11].reshape(2, 4, 8) for a in A]),
+                    alf_pre_y=np.stack([a[1].reshape(H, W) for a in A]), alf_pre_u=np.stack([a[2].reshape(H // 2, W // 2) for a in A]),
+                    alf_pre_v=np.stack([a[3].reshape(H // 2, W // 2) for a in A]),
+                    aps_meta=np.stack([r[0] for r in P]) if P else np.zeros((0, 16), np.int32), aps_luma=np.stack([r[1] for r in P]) if P else np.zeros((0, 675), np.int16),
+                    aps_chroma=np.stack([r[2] for r in P]) if P else np.zeros((0, 112), np.int16), aps_cc=np.stack([r[3] for r in P]) if P else np.zeros((0, 64), np.int16))
+        print("alf", tag, "on:", [a[0][4:7].tolist() for a in A], "luma APSs:", [int(a[0][7]) for a in A], "cc:", [a[0][17:19].tolist() for a in A],
+              "APSs per picture:", [sum(int(r[0][0]) == i for r in P) for i in range(frames)], "slice types:", [int(a[0][26]) for a in A])
+    np.savez_compressed(os.path.join(out_dir or os.path.join(ROOT, "tests/golden"), f"ref_inter_{tag}.npz"), **more, dims=np.array([W, H, depth, qp, frames], np.int32), meta=meta, cu=cu, lam=lam, sao=sao, src_crc=src_crc,
+                        motion=mot, refs=refs, rec_y=rec[0][:keep_rec], rec_u=rec[1][:keep_rec], rec_v=rec[2][:keep_rec], coeff=coeff if with_levels else coeff[:0], final_y=final[0], final_u=final[1],
                         final_v=final[2], trees=trees, models=models if with_levels else models[:0], models_inter=models_inter if with_levels else models_inter[:0],
                         # every call of uvg_search_cu_inter in coding order: frame, x, y, w, h, then the decided cu_info_t fields; its two costs
                         cuinter_i=np.stack([r[0] for r in CI]).astype(np.int32) if with_levels else np.zeros((0, 20), np.int32),
@@ -579,5 +613,10 @@ if __name__ == "__main__":
     inter(136, 72, 8, 51, 5, clip=True, suffix="_clip")           # every P / B picture clipped to QP 51 (rate_control.c CLIP_TO_QP)
     inter(136, 72, 10, 48, 9, extra=("gop", "8"), suffix="_ra8", clip=True)      # random access at a high QP, the QP offsets clipped
     inter(40, 24, 8, 27, 5, clip=True, suffix="_clip")            # a one-CTU picture: one partial CTU, the wavefront of one CTU (vectors leave it at the bottom)
+    # --alf full in the P / B picture loop (BASELINE configs[3] as written: --gop 16 with ALF on every picture).  No clip with a partial CTU
+    # had ALF on in any picture: the third one keeps the case "the SPS says ALF, every slice header says no" at such a size
+    inter(192, 128, 8, 22, 17, extra=("gop", "16"), suffix="_ra16", clip=True, alf=True, with_levels=False)      # new APSs in front of P / B pictures (the ids 7..0 wrap), 2 - 3 luma APSs of earlier pictures, chroma alternatives, a picture left alone
+    inter(192, 128, 10, 24, 9, clip=True, alf=True, with_levels=False)                                            # low delay, 10 bit: CC-ALF with per-CTU controls, 4 luma APSs, fixed filter sets, stale CTU flags under a slice that has ALF off
+    inter(136, 72, 8, 27, 17, extra=("gop", "16"), suffix="_ra16", clip=True, alf=True, with_levels=False)       # ALF off in every picture
     if not os.environ.get("GOLDENS_SKIP_CLIP120"):      # (ten minutes and 4 GB of records by itself)
         inter_crcs(1920, 1080, 8, 27, 120, extra=("owf", "1"), suffix="_owf1", clip=True)     # bench.py's c3_clip, picture by picture: BASELINE configs[2] as written, --owf 1 (frames in flight), crosses the second intra period at POC 64

@@ -717,6 +717,37 @@ class FramePool:
             self.L.uvghip_frame_pool_destroy(pool)
 
 
+def _alf_decide_callback(decide_one, failure):
+    """uvghip_alf_decide_fn over decide_one(i) -> the picture's decisions as a dict (ClosedLoop.alf_stage documents its keys): the library calls
+    back once per picture; the arrays stay valid until the next call, as the ABI asks.  An exception is kept in `failure` (it must not unwind
+    through the C frames) and the stage is refused."""
+    keep = []
+
+    def trampoline(user, i, picture, decision):
+        try:
+            d = decide_one(i)
+            opt = lambda key, dt: np.zeros(0, dt) if d.get(key) is None else np.ascontiguousarray(d[key], dt)      # (a disabled component's arrays may be absent / None)
+            arr = dict(luma_aps=np.ascontiguousarray(np.asarray(opt("luma_aps", np.int16)).reshape(-1, 677)[:int(d.get("n_luma_aps", 0))]) if int(d.get("n_luma_aps", 0)) else np.zeros(0, np.int16),
+                       chroma_aps=opt("chroma_aps", np.int16), cc_coeff=opt("cc_coeff", np.int16), ctu_flags=opt("ctu_flags", np.uint8),
+                       filter_set_idx=opt("filter_set_idx", np.int16))
+            keep[:] = [arr]
+            o = decision.contents
+            o.alf_type, o.n_luma_aps = int(d["alf_type"]), int(d.get("n_luma_aps", 0))
+            for c in range(3):
+                o.enabled[c] = int(d["enabled"][c])
+            for c in range(2):
+                o.cc_enabled[c], o.cc_filter_count[c] = int(d.get("cc_enabled", (0, 0))[c]), int(d.get("cc_filter_count", (0, 0))[c])
+            for k, a in arr.items():
+                setattr(o, k, a.ctypes.data if a.size else None)
+            return 0
+        except Exception as e:                            # noqa: BLE001
+            failure.append(e)
+            return 1
+    cb = _lib.ALF_DECIDE_FN(trampoline)
+    cb._keep = keep
+    return cb
+
+
 class ClosedLoop(CtuSearch):
     """uvghip_loop_plan_*: the search of CtuSearch followed by the in-loop filters on the reference's schedule, one call per
     group of pictures.  Adds out[i] = (y, u, v), the pictures after deblocking + SAO, and after a run sao_info ([n, ctus, 2, 17]
@@ -951,7 +982,7 @@ class ClosedLoop(CtuSearch):
         torch.cuda.synchronize()          # (the decisions' device copies go out of scope with this call)
         return out, nbytes
 
-    def alf_stage(self, decide, source=None, classification_shift=None):
+    def alf_stage(self, decide, source=None, classification_shift=None, alf_out=None, stream=None):
         """uvghip_loop_plan_alf_stage: the ALF stage of the picture loop (BASELINE configs[3]: --alf full), after run(): for every picture of the plan
           1. the frame's ALF statistics from the loop's SAO output on the device, handed over on demand (AlfStatistics: classification,
              luma covariance per class and CTU, chroma covariance, CC-ALF covariance -- what alf_derive_stats_for_filtering leaves, alf.c:4227),
@@ -963,43 +994,22 @@ class ClosedLoop(CtuSearch):
           3. uvghip_alf_reconstruct_picture on the SAO output -> alf_out[i], the picture the encoder returns and hashes,
           4. uvghip_encode_slice_rows_alf: the slice data with the CTU-level ALF syntax.
         -> (alf_out: per picture three device planes, rows [n, n_rows, row_cap] uint8, row_bytes [n, n_rows] int32).  source: the plan's
-        source pictures (the statistics compare with them); classification_shift: cfg.input_bitdepth + 4 (alf.c:5185; default depth + 4)."""
+        source pictures (the statistics compare with them); classification_shift: cfg.input_bitdepth + 4 (alf.c:5185; default depth + 4).
+        alf_out: per picture three device planes to write instead of new ones (LowDelayLoop: later pictures hold their addresses as references)."""
         shift = self.depth + 4 if classification_shift is None else classification_shift
         dev = self.loop_ws.device
         W, H = int(self.P.pic_w), int(self.P.pic_h)
-        self.alf_out = [[torch.empty_like(p) for p in self.out[i]] for i in range(self.n)]
+        self.alf_out = [[torch.empty_like(p) for p in self.out[i]] for i in range(self.n)] if alf_out is None else alf_out
         planes = (_lib.AlfPlanes * self.n)()
         for i, o in enumerate(self.alf_out):
             planes[i] = _lib.AlfPlanes(_dev(o[0]), _dev(o[1]), _dev(o[2]), o[0].stride(0), o[1].stride(0))
-        keep, failure = [], []
-
-        def trampoline(user, i, picture, decision):          # uvghip_alf_decide_fn: the library calls back once per picture
-            try:
-                stats = AlfStatistics(self.out[i], None if source is None else source[i], W, H, shift)
-                d = decide(i, stats)
-                opt = lambda key, dt: np.zeros(0, dt) if d.get(key) is None else np.ascontiguousarray(d[key], dt)      # (a disabled component's arrays may be absent / None)
-                arr = dict(luma_aps=np.ascontiguousarray(np.asarray(opt("luma_aps", np.int16)).reshape(-1, 677)[:int(d.get("n_luma_aps", 0))]) if int(d.get("n_luma_aps", 0)) else np.zeros(0, np.int16),
-                           chroma_aps=opt("chroma_aps", np.int16), cc_coeff=opt("cc_coeff", np.int16), ctu_flags=opt("ctu_flags", np.uint8),
-                           filter_set_idx=opt("filter_set_idx", np.int16))
-                keep[:] = [arr]                               # (valid until the next call, as the ABI asks)
-                o = decision.contents
-                o.alf_type, o.n_luma_aps = int(d["alf_type"]), int(d.get("n_luma_aps", 0))
-                for c in range(3):
-                    o.enabled[c] = int(d["enabled"][c])
-                for c in range(2):
-                    o.cc_enabled[c], o.cc_filter_count[c] = int(d.get("cc_enabled", (0, 0))[c]), int(d.get("cc_filter_count", (0, 0))[c])
-                for k, a in arr.items():
-                    setattr(o, k, a.ctypes.data if a.size else None)
-                return 0
-            except Exception as e:                            # noqa: BLE001 -- an exception must not unwind through the C frames
-                failure.append(e)
-                return 1
-        cb = _lib.ALF_DECIDE_FN(trampoline)
+        failure = []
+        cb = _alf_decide_callback(lambda i: decide(i, AlfStatistics(self.out[i], None if source is None else source[i], W, H, shift)), failure)
         row_cap = 3 * 64 * W * (1 if self.depth == 8 else 2)
         rows = torch.empty((self.n, self.hc, row_cap), dtype=torch.uint8, device=dev)
         nbytes = torch.zeros((self.n, self.hc), dtype=torch.int32, device=dev)
         ws = torch.empty(self.L.uvghip_loop_plan_alf_workspace_bytes(self.loop), dtype=torch.uint8, device=dev)
-        rc = self.L.uvghip_loop_plan_alf_stage(self.loop, cb, None, shift, ctypes.byref(planes), _dev(ws), _dev(rows), row_cap, _dev(nbytes), _stream())
+        rc = self.L.uvghip_loop_plan_alf_stage(self.loop, cb, None, shift, ctypes.byref(planes), _dev(ws), _dev(rows), row_cap, _dev(nbytes), _stream() if stream is None else stream)
         if failure:
             raise failure[0]
         _lib.check(rc, "uvghip_loop_plan_alf_stage")
@@ -1247,6 +1257,37 @@ def loop_pb_run(pictures, depth, sao_type=3, stream=None):
             view(c, n * nr.value * cap.value).view(n, nr.value, cap.value), view(d, n * nr.value * 4).view(torch.int32).view(n, nr.value))
 
 
+def loop_pb_alf_stage(pictures, depth, loop_ws, decide, sao_out, alf_out, source=None, sao_type=3, classification_shift=None, stream=None):
+    """uvghip_loop_pb_alf_stage: the ALF stage behind loop_pb_run on the same pictures (list or ctypes array of lib.LoopPbPicture) and its
+    workspace loop_ws.  decide(i, stats) -> the decisions of picture i as ClosedLoop.alf_stage takes them (stats: AlfStatistics over sao_out[i] --
+    the three planes pictures[i].out_* point to, the picture ALF gets -- and source[i]); alf_out: per picture three device planes the stage writes -- what later pictures must be given as
+    references.  -> (rows [n, n_rows, row_cap] uint8, row_bytes [n, n_rows] int32): the slice data with the CTU-level ALF syntax.  Waits for the
+    stream (the stage's workspace goes out of scope with the call)."""
+    n = len(pictures)
+    L = _lib.init(torch.cuda.current_device())
+    arr = pictures if isinstance(pictures, ctypes.Array) else (_lib.LoopPbPicture * n)(*pictures)
+    W, H = int(arr[0].search.params.pic_w), int(arr[0].search.params.pic_h)
+    shift = depth + 4 if classification_shift is None else classification_shift
+    dev = loop_ws.device
+    failure = []
+    cb = _alf_decide_callback(lambda i: decide(i, AlfStatistics(sao_out[i], None if source is None else source[i], W, H, shift)), failure)
+    planes = (_lib.AlfPlanes * n)()
+    for i, o in enumerate(alf_out):
+        planes[i] = _lib.AlfPlanes(_dev(o[0]), _dev(o[1]), _dev(o[2]), o[0].stride(0), o[1].stride(0))
+    hc = (H + 63) // 64
+    row_cap = 3 * 64 * W * (1 if depth == 8 else 2)
+    rows = torch.empty((n, hc, row_cap), dtype=torch.uint8, device=dev)
+    nbytes = torch.zeros((n, hc), dtype=torch.int32, device=dev)
+    ws = torch.empty(L.uvghip_loop_pb_alf_workspace_bytes(depth, n, W, H), dtype=torch.uint8, device=dev)
+    rc = L.uvghip_loop_pb_alf_stage(depth, ctypes.byref(arr), n, sao_type, _dev(loop_ws), cb, None, shift, ctypes.byref(planes), _dev(ws), _dev(rows), row_cap, _dev(nbytes),
+                                    _stream() if stream is None else stream)
+    if failure:
+        raise failure[0]
+    _lib.check(rc, "uvghip_loop_pb_alf_stage")
+    torch.cuda.synchronize()
+    return rows, nbytes
+
+
 def reference_dag(frames):
     """The dependencies between the coded pictures of a sequence: frames = one dict per picture in CODING order with slice_type (2 I, 1 P,
     0 B), poc, n_refs, ref_pocs (the reference buffer the encoder coded the picture with: uvg_encoder_create_ref_lists) ->
@@ -1327,8 +1368,13 @@ class LowDelayLoop:
     temporal layer, and of neighbouring GOPs, run side by side on k streams (deps[f]: the coded pictures f reads)."""
 
     def __init__(self, W, H, depth, n_seq, frames, src, sao_type=3, tmvp=1, max_merge=6, merge_level=2, bipred=1, fme_level=4, early_skip=1, by_level=False, rd=0, inflight_margin=0,
-                 inflight=False, intra_in_flight=False):
-        """intra_in_flight (with inflight): the I pictures are part of the flight too -- their search runs as a few persistent workgroups on a
+                 inflight=False, intra_in_flight=False, alf=None, alf_shift=None):
+        """alf: decide(f, s, stats) -> the ALF decisions of coded picture f of sequence s (a dict as ClosedLoop.alf_stage takes it; stats:
+        AlfStatistics) -- the stream has --alf on.  Every step, an I step through ClosedLoop.alf_stage or a P / B step through
+        uvghip_loop_pb_alf_stage, is followed by its ALF stage before anything that references it is issued: by_poc and out[f][s] hold the ALF
+        outputs (what the encoder predicts from), sao_out[f][s] the pictures ALF got, rows / row_bytes the rows coded with the ALF syntax.
+        alf_shift: the classification shift, cfg.input_bitdepth + 4 (default depth + 4).  Not with inflight (see below).
+        intra_in_flight (with inflight): the I pictures are part of the flight too -- their search runs as a few persistent workgroups on a
         second stream BESIDE the in-flight launch, which filters them CTU by CTU as they are searched (uvghip_loop_pb_run_inflight_intra), so the
         P / B pictures behind an I picture follow it four diagonals behind instead of waiting for the whole picture.
         inflight: the encoder's --owf schedule (encoderstate.c:1060-1116): ALL P / B pictures go through ONE uvghip_loop_pb_run_inflight -- a
@@ -1341,7 +1387,11 @@ class LowDelayLoop:
         by_level: the P / B pictures that sit at the same depth of the reference DAG (deps) go through ONE uvghip_loop_pb_run together --
         the pictures of one temporal layer of a random-access GOP, and of neighbouring GOPs, share a launch (their wavefronts interleave in the
         search kernel); a low-delay sequence has one picture per level and is unchanged."""
+        if alf is not None and inflight:
+            raise ValueError("LowDelayLoop: alf with inflight=True -- the ALF derivation needs the statistics of the whole picture, and later pictures predict from "
+                             "the ALF output: a picture cannot start on the CTUs of a reference whose ALF stage has not run (the in-flight entry points take no ALF argument)")
         self.W, self.H, self.depth, self.n_seq, self.frames, self.sao_type = W, H, depth, n_seq, frames, sao_type
+        self.alf, self.alf_shift, self.src, self.sao_out = alf, depth + 4 if alf_shift is None else alf_shift, src, []
         wc, hc = (W + 63) // 64, (H + 63) // 64
         ctus, n4 = wc * hc, hc * 16 * wc * 16
         self.hc = hc
@@ -1408,6 +1458,9 @@ class LowDelayLoop:
                 L = _lib.init(torch.cuda.current_device())
                 ws = None if inflight else z(L.uvghip_loop_pb_workspace_bytes(depth, n_seq, W, H), torch.uint8)
                 self.steps.append(("PB", arr, ws, bufs))
+            self.sao_out.append(outs)
+            if alf is not None:          # the planes the ALF stage writes: the pictures later ones reference
+                outs = [tuple(torch.zeros_like(p) for p in o) for o in outs]
             for s in range(n_seq):
                 by_poc[(s, fs["poc"])] = (outs[s], mots[s])
             coded_as[fs["poc"]] = f
@@ -1515,6 +1568,10 @@ class LowDelayLoop:
                         mots[s][:, :, 0] = loop.cu[s][:, :, 2].to(torch.int32)
                         mots[s][:, :, 6:8] = -1
                 rows, nb = loop.slice_data()
+                if self.alf is not None:
+                    at = lambda i: (fl[i // self.n_seq], i % self.n_seq)
+                    _, rows, nb = loop.alf_stage(lambda i, stats: self.alf(*at(i), stats), source=[self.src[at(i)[1]][at(i)[0]] for i in range(loop.n)],
+                                                 classification_shift=self.alf_shift, alf_out=[self.out[at(i)[0]][at(i)[1]] for i in range(loop.n)], stream=st)
                 for j, g in enumerate(fl):
                     self.rows[g], self.row_bytes[g] = rows[j * self.n_seq:(j + 1) * self.n_seq], nb[j * self.n_seq:(j + 1) * self.n_seq]
             else:
@@ -1525,6 +1582,11 @@ class LowDelayLoop:
                 else:
                     _lib.check(self.L.uvghip_loop_pb_run(self.depth, ctypes.byref(arr), n, self.sao_type, _dev(ws), st), "uvghip_loop_pb_run")
                 rows, row_bytes = self._pb_slice_data(kind, ws, n)
+                if self.alf is not None:
+                    at = lambda i: (fr[i // self.n_seq], i % self.n_seq)
+                    rows, row_bytes = loop_pb_alf_stage(arr, self.depth, ws, lambda i, stats: self.alf(*at(i), stats), [self.sao_out[at(i)[0]][at(i)[1]] for i in range(n)],
+                                                        [self.out[at(i)[0]][at(i)[1]] for i in range(n)], source=[self.src[at(i)[1]][at(i)[0]] for i in range(n)],
+                                                        sao_type=self.sao_type, classification_shift=self.alf_shift, stream=st)
                 for j, g in enumerate(fr):
                     self.rows[g], self.row_bytes[g] = rows[j * self.n_seq:(j + 1) * self.n_seq], row_bytes[j * self.n_seq:(j + 1) * self.n_seq]
             if in_flight > 1:

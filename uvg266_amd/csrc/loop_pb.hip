@@ -169,6 +169,122 @@ extern "C" int uvghip_loop_pb_run(int bitdepth, const uvghip_loop_pb_picture_t *
   return 0;
 }
 
+// ---- the ALF stage behind uvghip_loop_pb_run (BASELINE configs[3]: --gop 16 --alf full), on the same pictures and loop workspace: where the
+// encoder runs uvg_alf_enc_process (src/alf.c:5193) on a P / B picture and then codes its CTUs for real (src/encoderstate.c:1043-1052).  The
+// decisions come from the caller's `decide` as in uvghip_loop_plan_alf_stage; alf_out[i] is what later pictures predict from. ----
+namespace {
+struct alf_layout_t { size_t rec, coder, flags, per, total; };
+alf_layout_t alf_layout_of(int n, int w, int h)
+{
+  const size_t ctus = (size_t)((w + 63) / 64) * ((h + 63) / 64);
+  alf_layout_t A;
+  uvgi_carver c;
+  A.rec = c.take(uvghip_alf_reconstruct_workspace_bytes(w, h));
+  A.coder = c.take(uvghip_slice_rows_pb_alf_workspace_bytes(n));
+  A.per = uvgi_align_up(ctus * 7 + (ctus & 1) + ctus * sizeof(int16_t), 256);          // per picture: ctu_flags [7][ctus], filter_set_idx [ctus]
+  A.flags = c.take((size_t)n * A.per);
+  A.total = c.at;
+  return A;
+}
+}  // namespace
+
+extern "C" size_t uvghip_loop_pb_alf_workspace_bytes(int bitdepth, int n_pictures, int pic_w, int pic_h)
+{
+  if ((bitdepth != 8 && bitdepth != 10) || n_pictures <= 0 || pic_w <= 0 || pic_h <= 0) return 0;
+  return alf_layout_of(n_pictures, pic_w, pic_h).total;
+}
+
+extern "C" int uvghip_loop_pb_alf_stage(int bitdepth, const uvghip_loop_pb_picture_t *pictures, int n_pictures, int sao_type, void *loop_workspace, uvghip_alf_decide_fn decide,
+                                        void *user, int classification_shift, const uvghip_alf_planes_t *alf_out, void *workspace, uint8_t *rows, int row_cap, int32_t *row_bytes,
+                                        void *stream)
+{
+  UVGHIP_REQUIRE_READY();
+  UVGHIP_REQUIRE_DEPTH(bitdepth);
+  if (!pictures || n_pictures <= 0 || sao_type < 0 || sao_type > 3 || !loop_workspace || !decide || !alf_out || !workspace || !rows || row_cap <= 0 || !row_bytes ||
+      classification_shift < 8 || classification_shift > 20)
+    return uvghip_set_error(hipErrorInvalidValue, __func__);
+  const int w = pictures[0].search.params.pic_w, h = pictures[0].search.params.pic_h;
+  if (w <= 0 || h <= 0) return uvghip_set_error(hipErrorInvalidValue, __func__);
+  const layout_t L = layout_of(bitdepth, n_pictures, w, h);
+  const alf_layout_t A = alf_layout_of(n_pictures, w, h);
+  const unsigned char *lws = static_cast<const unsigned char *>(loop_workspace);
+  unsigned char *ws = static_cast<unsigned char *>(workspace);
+  hipStream_t st = uvghip_stream(stream);
+  const int wc = (w + 63) / 64, hc = (h + 63) / 64, ctus = wc * hc;
+  const size_t b = bitdepth == 8 ? 1 : 2;
+  const int32_t *sao_info = reinterpret_cast<const int32_t *>(lws + L.tail.info);
+  const uint16_t *sao_models = reinterpret_cast<const uint16_t *>(lws + L.tail.models);
+  std::vector<uvghip_slice_alf_t> sa(n_pictures);
+  for (int i = 0; i < n_pictures; ++i) {
+    const uvghip_loop_pb_picture_t &q = pictures[i];
+    const uvghip_alf_planes_t &o = alf_out[i];
+    if (q.search.params.pic_w != w || q.search.params.pic_h != h) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_alf_stage: a picture's size differs from the first one's");
+    if (int rc = uvgi_check_out_planes(q, w, "uvghip_loop_pb_alf_stage: the loop's output planes")) return rc;
+    if (!o.y || !o.u || !o.v || o.stride < w || o.stride_c < w / 2) return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_alf_stage: output planes");
+    uvghip_loop_picture_t view;
+    memset(&view, 0, sizeof view);
+    view.search = q.search.pic;
+    view.out_y = q.out_y; view.out_u = q.out_u; view.out_v = q.out_v; view.out_stride = q.out_stride; view.out_stride_c = q.out_stride_c;
+    uvghip_alf_decision_t d;
+    memset(&d, 0, sizeof d);
+    if (int rc = decide(user, i, &view, &d)) return uvghip_set_error(hipErrorInvalidValue, rc > 0 ? "uvghip_loop_pb_alf_stage: decide() failed" : "uvghip_loop_pb_alf_stage: decide() refused");
+    const bool any = d.enabled[0] || d.enabled[1] || d.enabled[2] || d.cc_enabled[0] || d.cc_enabled[1];
+    if ((d.alf_type != 1 && d.alf_type != 2) || d.n_luma_aps < 0 || d.n_luma_aps > 8 || (any && (!d.ctu_flags || !d.filter_set_idx)) || (d.n_luma_aps && !d.luma_aps) ||
+        ((d.enabled[1] || d.enabled[2]) && !d.chroma_aps) || ((d.cc_enabled[0] || d.cc_enabled[1]) && !d.cc_coeff))
+      return uvghip_set_error(hipErrorInvalidValue, "uvghip_loop_pb_alf_stage: the decision decide() returned");
+    if (any) {
+      uvghip_alf_picture_t a;
+      memset(&a, 0, sizeof a);
+      a.in_y = q.out_y; a.in_u = q.out_u; a.in_v = q.out_v; a.in_stride = q.out_stride; a.in_stride_c = q.out_stride_c;
+      a.out_y = o.y; a.out_u = o.u; a.out_v = o.v; a.out_stride = o.stride; a.out_stride_c = o.stride_c;
+      a.width = w; a.height = h;
+      for (int c = 0; c < 3; ++c) a.slice_enabled[c] = d.enabled[c];
+      a.n_luma_aps = d.n_luma_aps; a.ctu_flags = d.ctu_flags; a.filter_set_idx = d.filter_set_idx; a.luma_aps = d.luma_aps; a.chroma_aps = d.chroma_aps;
+      a.alf_full = d.alf_type == 2; a.cc_alf_enabled[0] = d.cc_enabled[0]; a.cc_alf_enabled[1] = d.cc_enabled[1]; a.cc_coeff = d.cc_coeff;
+      a.classification_shift = classification_shift;
+      if (int rc = uvghip_alf_reconstruct_picture(bitdepth, &a, ws + A.rec, stream)) return rc;
+    } else {          // a picture ALF leaves alone
+      UVGHIP_TRY(hipMemcpy2DAsync(o.y, (size_t)o.stride * b, q.out_y, (size_t)q.out_stride * b, (size_t)w * b, h, hipMemcpyDeviceToDevice, st));
+      UVGHIP_TRY(hipMemcpy2DAsync(o.u, (size_t)o.stride_c * b, q.out_u, (size_t)q.out_stride_c * b, (size_t)(w / 2) * b, h / 2, hipMemcpyDeviceToDevice, st));
+      UVGHIP_TRY(hipMemcpy2DAsync(o.v, (size_t)o.stride_c * b, q.out_v, (size_t)q.out_stride_c * b, (size_t)(w / 2) * b, h / 2, hipMemcpyDeviceToDevice, st));
+    }
+    // the slice's side of the decision: the flags and set indices on the device, where the coder reads them
+    uvghip_slice_alf_t &s = sa[i];
+    memset(&s, 0, sizeof s);
+    s.alf_type = d.alf_type; s.n_luma_aps = d.n_luma_aps; s.n_alternatives_chroma = d.chroma_aps ? d.chroma_aps[112] : 0;
+    for (int c = 0; c < 3; ++c) s.enabled[c] = d.enabled[c];
+    for (int c = 0; c < 2; ++c) { s.cc_enabled[c] = d.cc_enabled[c]; s.cc_filter_count[c] = d.cc_filter_count[c]; }
+    if (any) {
+      unsigned char *fl = ws + A.flags + (size_t)i * A.per, *si = fl + (size_t)ctus * 7 + ((size_t)ctus & 1);
+      UVGHIP_TRY(hipMemcpyAsync(fl, d.ctu_flags, (size_t)ctus * 7, hipMemcpyHostToDevice, st));
+      UVGHIP_TRY(hipMemcpyAsync(si, d.filter_set_idx, (size_t)ctus * sizeof(int16_t), hipMemcpyHostToDevice, st));
+      UVGHIP_TRY(hipStreamSynchronize(st));          // (decide()'s arrays need not outlive the next call)
+      s.ctu_flags = fl; s.filter_set_idx = reinterpret_cast<const int16_t *>(si);
+    }
+  }
+  // the slice data, run by run as uvghip_loop_pb_run codes it (pictures that share QP, lambda and slice type)
+  for (int i0 = 0; i0 < n_pictures;) {
+    const uvghip_ctu_pb_picture_t &s0 = pictures[i0].search;
+    int i1 = i0 + 1;
+    while (i1 < n_pictures && pictures[i1].search.params.qp == s0.params.qp && pictures[i1].search.params.lambda == s0.params.lambda &&
+           pictures[i1].search.slice_type == s0.slice_type && pictures[i1].search.frame_qp == s0.frame_qp)
+      ++i1;
+    const int m = i1 - i0;
+    const size_t o0 = (size_t)i0 * ctus;
+    std::vector<uvghip_ctu_picture_t> cp(m);
+    std::vector<uvghip_slice_pb_t> sl(m);
+    for (int i = i0; i < i1; ++i) {
+      cp[i - i0] = pictures[i].search.pic; sl[i - i0] = uvgi_slice_pb_of(pictures[i].search);
+      sl[i - i0].second_pass = 1;          // the encoder's real coding pass behind ALF follows a simulated one (uvghip_slice_pb_t)
+    }
+    if (int rc = uvghip_encode_slice_rows_pb_alf(bitdepth, &s0.params, cp.data(), sl.data(), sa.data() + i0, m, sao_type ? sao_info + o0 * 34 : nullptr,
+                                                 sao_type ? sao_models + o0 * 6 : nullptr, ws + A.coder, rows + (size_t)i0 * hc * row_cap, row_cap, row_bytes + (size_t)i0 * hc, stream))
+      return rc;
+    i0 = i1;
+  }
+  return 0;
+}
+
 // ---- pictures in flight behind their references: one call = one persistent launch for the whole DAG (uvgi_search_pb_inflight: the
 // search with the per-CTU filters inside), then ONE coder launch over all pictures -- their QPs, lambdas and slice types may differ ----
 extern "C" size_t uvghip_loop_pb_inflight_workspace_bytes(int bitdepth, int n_pictures, int pic_w, int pic_h)

@@ -12,6 +12,7 @@
 // The parameter sets and the version SEI are the encoder's (control plane): they do not depend on the picture.
 #include "uvghip_common.h"
 #include <cstring>
+#include <string>
 
 namespace {
 
@@ -134,6 +135,46 @@ void write_alf_aps(nal_writer &w, const uvghip_alf_aps_t &a, int alf_full, bool 
   w.align_with_one();                // rbsp_trailing_bits
 }
 
+// What every writer of an --alf stream checks of its ALF arguments; `who`: the entry point, for the error text.
+int check_alf_args(const char *who, const uvghip_alf_slice_t *alf, const uvghip_alf_aps_t *aps, int n_aps)
+{
+  const std::string name(who);
+  if (!alf || n_aps < 0 || (n_aps && !aps)) return uvghip_set_error(hipErrorInvalidValue, (name + ": alf / aps").c_str());
+  if ((alf->alf_type != 1 && alf->alf_type != 2) || alf->n_luma_aps < 0 || alf->n_luma_aps > 7)
+    return uvghip_set_error(hipErrorInvalidValue, (name + ": the slice's ALF fields (alf_type 1 / 2, at most 7 luma APSs)").c_str());
+  for (int i = 0; i < n_aps; ++i)
+    if (aps[i].aps_id < 0 || aps[i].aps_id > 7 || (aps[i].new_filter[0] && (!aps[i].luma || aps[i].num_luma_filters < 1 || aps[i].num_luma_filters > 25)) ||
+        (aps[i].new_filter[1] && (!aps[i].chroma || aps[i].num_alternatives_chroma < 1 || aps[i].num_alternatives_chroma > 8)) ||
+        ((aps[i].new_cc_filter[0] || aps[i].new_cc_filter[1]) && !aps[i].cc) || aps[i].cc_filter_count[0] > 4 || aps[i].cc_filter_count[1] > 4)
+      return uvghip_set_error(hipErrorInvalidValue, (name + ": a parameter set").c_str());
+  return 0;
+}
+
+// the APS NAL units in front of the slice (uvg_encode_alf_adaptive_parameter_set, encoder_state-bitstream.c:1562); first_nal: no NAL unit of
+// the access unit has been written yet -- the first one takes the long start code (:1519)
+void write_alf_apss(nal_writer &w, const uvghip_alf_slice_t &alf, const uvghip_alf_aps_t *aps, int n_aps, bool &first_nal)
+{
+  for (int i = 0; i < n_aps; ++i) { write_alf_aps(w, aps[i], alf.alf_type == 2, first_nal); first_nal = false; }
+  w.zeros = 0;
+}
+
+// the slice header's ALF fields (encoder_state-bitstream.c:1283-1325): behind sh_slice_type / sh_no_output_of_prior_pics_flag, in front of
+// the reference picture lists
+void write_alf_slice_fields(nal_writer &w, const uvghip_alf_slice_t &alf)
+{
+  w.bits(alf.enabled[0] != 0, 1);    // slice_alf_enabled_flag
+  if (!alf.enabled[0]) return;
+  w.bits((uint32_t)alf.n_luma_aps, 3);
+  for (int i = 0; i < alf.n_luma_aps; ++i) w.bits((uint32_t)alf.luma_aps_id[i], 3);
+  w.bits(alf.enabled[1] != 0, 1); w.bits(alf.enabled[2] != 0, 1);
+  if (alf.enabled[1] || alf.enabled[2]) w.bits((uint32_t)alf.chroma_aps_id, 3);
+  if (alf.alf_type == 2)
+    for (int c = 0; c < 2; ++c) {
+      w.bits(alf.cc_enabled[c] != 0, 1);
+      if (alf.cc_enabled[c]) w.bits((uint32_t)alf.cc_aps_id[c], 3);
+    }
+}
+
 // entry points, byte alignment, the rows' substreams, then the decoded picture hash SEI (shared by both writers)
 void finish_picture(nal_writer &w, uint8_t *out, size_t cap, const uint8_t *rows, size_t row_pitch, const int32_t *row_bytes, int n_rows, int32_t longest,
                     const uint32_t *checksum)
@@ -247,53 +288,42 @@ extern "C" int uvghip_write_idr_nals_ra(int poc, int poc_lsb_bits, int qp_delta,
 // ... of an --alf on / --alf full stream: the APS NAL units the picture is preceded by (uvg_encode_alf_adaptive_parameter_set, alf.c:1610; written
 // between the parameter sets / the start of the access unit and the slice, encoder_state-bitstream.c:1562) and the slice header's ALF
 // fields (:1283-1330).  Host function.
-extern "C" int uvghip_write_idr_nals_alf(int poc, int qp_delta, int sao, const uvghip_alf_slice_t *alf, const uvghip_alf_aps_t *aps, int n_aps, const uint8_t *rows,
-                                         size_t row_pitch, const int32_t *row_bytes, int n_rows, const uint32_t *checksum, uint8_t *out, size_t cap, size_t *len)
+static int write_idr_picture_alf(const char *who, int nal_type, int poc, int poc_lsb_bits, int qp_delta, int sao, const uvghip_alf_slice_t *alf, const uvghip_alf_aps_t *aps, int n_aps,
+                                 const uint8_t *rows, size_t row_pitch, const int32_t *row_bytes, int n_rows, const uint32_t *checksum, uint8_t *out, size_t cap, size_t *len)
 {
-  if (!rows || !row_bytes || n_rows <= 0 || !len || (!out && cap) || poc < 0 || !alf || n_aps < 0 || (n_aps && !aps) || (alf->alf_type != 1 && alf->alf_type != 2) ||
-      alf->n_luma_aps < 0 || alf->n_luma_aps > 7)
-    return uvghip_set_error(hipErrorInvalidValue, __func__);
-  for (int i = 0; i < n_aps; ++i)
-    if (aps[i].aps_id < 0 || aps[i].aps_id > 7 || (aps[i].new_filter[0] && (!aps[i].luma || aps[i].num_luma_filters < 1 || aps[i].num_luma_filters > 25)) ||
-        (aps[i].new_filter[1] && (!aps[i].chroma || aps[i].num_alternatives_chroma < 1 || aps[i].num_alternatives_chroma > 8)) ||
-        ((aps[i].new_cc_filter[0] || aps[i].new_cc_filter[1]) && !aps[i].cc) || aps[i].cc_filter_count[0] > 4 || aps[i].cc_filter_count[1] > 4)
-      return uvghip_set_error(hipErrorInvalidValue, "uvghip_write_idr_nals_alf: a parameter set");
+  const std::string name(who);
+  if (!rows || !row_bytes || n_rows <= 0 || !len || (!out && cap) || poc < 0 || poc_lsb_bits < 4 || poc_lsb_bits > 16) return uvghip_set_error(hipErrorInvalidValue, who);
+  if (int rc = check_alf_args(who, alf, aps, n_aps)) return rc;
   int32_t longest = 0;
   for (int r = 0; r < n_rows; ++r) {
-    if (row_bytes[r] <= 0 || (size_t)row_bytes[r] > row_pitch) return uvghip_set_error(hipErrorInvalidValue, "uvghip_write_idr_nals_alf: a row is empty or longer than its slot");
+    if (row_bytes[r] <= 0 || (size_t)row_bytes[r] > row_pitch) return uvghip_set_error(hipErrorInvalidValue, (name + ": a row is empty or longer than its slot").c_str());
     if (row_bytes[r] > longest) longest = row_bytes[r];
   }
   nal_writer w = {out, cap, 0, 0, 0, 0};
   bool first_nal = poc != 0;         // picture 0 follows the parameter sets in its access unit; later pictures open theirs (long start code on the first NAL unit)
-  for (int i = 0; i < n_aps; ++i) { write_alf_aps(w, aps[i], alf->alf_type == 2, first_nal); first_nal = false; }
-  w.zeros = 0;
-  if (poc == 0) w.start(NAL_IDR_N_LP); else w.start(NAL_IDR_W_RADL, first_nal);
+  write_alf_apss(w, *alf, aps, n_aps, first_nal);
+  w.start(nal_type, first_nal);
   w.bits(1, 1);                      // sh_picture_header_in_slice_header_flag
   w.bits(1, 1);                      // ph_gdr_or_irap_pic_flag
   w.bits(0, 1);                      // ph_non_ref_pic_flag
   w.bits(0, 1);                      // ph_gdr_pic_flag
   w.bits(0, 1);                      // ph_inter_slice_allowed_flag
   w.ue(0);                           // ph_pic_parameter_set_id
-  w.bits((uint32_t)poc & 15u, 4);    // ph_pic_order_cnt_lsb
+  w.bits((uint32_t)poc & ((1u << poc_lsb_bits) - 1u), poc_lsb_bits);      // ph_pic_order_cnt_lsb
   w.bits(0, 1);                      // sh_no_output_of_prior_pics_flag
-  w.bits(alf->enabled[0] != 0, 1);   // slice_alf_enabled_flag
-  if (alf->enabled[0]) {
-    w.bits((uint32_t)alf->n_luma_aps, 3);
-    for (int i = 0; i < alf->n_luma_aps; ++i) w.bits((uint32_t)alf->luma_aps_id[i], 3);
-    w.bits(alf->enabled[1] != 0, 1); w.bits(alf->enabled[2] != 0, 1);
-    if (alf->enabled[1] || alf->enabled[2]) w.bits((uint32_t)alf->chroma_aps_id, 3);
-    if (alf->alf_type == 2)
-      for (int c = 0; c < 2; ++c) {
-        w.bits(alf->cc_enabled[c] != 0, 1);
-        if (alf->cc_enabled[c]) w.bits((uint32_t)alf->cc_aps_id[c], 3);
-      }
-  }
+  write_alf_slice_fields(w, *alf);
   w.se(qp_delta);                    // sh_qp_delta
   if (sao) w.bits(3, 2);             // sh_sao_luma_used_flag, sh_sao_chroma_used_flag
   finish_picture(w, out, cap, rows, row_pitch, row_bytes, n_rows, longest, checksum);
   *len = w.n;
-  if (w.n > cap) return uvghip_set_error(hipErrorInvalidValue, "uvghip_write_idr_nals_alf: the output buffer is too small (see *len)");
+  if (w.n > cap) return uvghip_set_error(hipErrorInvalidValue, (name + ": the output buffer is too small (see *len)").c_str());
   return 0;
+}
+
+extern "C" int uvghip_write_idr_nals_alf(int poc, int qp_delta, int sao, const uvghip_alf_slice_t *alf, const uvghip_alf_aps_t *aps, int n_aps, const uint8_t *rows,
+                                         size_t row_pitch, const int32_t *row_bytes, int n_rows, const uint32_t *checksum, uint8_t *out, size_t cap, size_t *len)
+{
+  return write_idr_picture_alf(__func__, poc == 0 ? NAL_IDR_N_LP : NAL_IDR_W_RADL, poc, 4, qp_delta, sao, alf, aps, n_aps, rows, row_pitch, row_bytes, n_rows, checksum, out, cap, len);
 }
 
 // The same for a P / B picture (TRAIL pictures, temporal id 0: uvg266 only signals a sub-layer for STSA pictures, :1484): the picture
@@ -303,9 +333,11 @@ extern "C" int uvghip_write_idr_nals_alf(int poc, int qp_delta, int sao, const u
 // signalled as a copy of list 0's entries (copy_rpl1 = (gop_lowdelay || !gop_len) && bipred, :1165).  delta_neg / delta_pos: the POC
 // distance of each reference picture, in the order of the GOP structure's ref_neg[] / ref_pos[] (src/gop.h, uvg_config_process_lp_gop
 // src/cfg.c:1640-1720: ascending) restricted to the pictures that are in the reference buffer (:1176-1190).
+// alf: the slice's ALF fields and the APS NAL units in front of it, for a stream whose SPS has ALF on (NULL: it has not -- no flag at all).
 static int write_inter_picture(const char *who, int nal_type, int poc, int poc_lsb_bits, int slice_type, int n_ref_neg, const int32_t *delta_neg, int n_ref_pos, const int32_t *delta_pos,
                                int copy_rpl1, int tmvp, int qp_delta, int sao, const uint8_t *rows, size_t row_pitch, const int32_t *row_bytes, int n_rows,
-                               const uint32_t *checksum, uint8_t *out, size_t cap, size_t *len)
+                               const uint32_t *checksum, uint8_t *out, size_t cap, size_t *len, const uvghip_alf_slice_t *alf = nullptr, const uvghip_alf_aps_t *aps = nullptr,
+                               int n_aps = 0)
 {
   // (a CRA picture is an I slice with the reference buffer of the pictures that follow it in its lists; every other picture here is P or B)
   if (!rows || !row_bytes || n_rows <= 0 || !len || (!out && cap) || poc < 0 || poc_lsb_bits < 4 || poc_lsb_bits > 16 ||
@@ -326,7 +358,9 @@ static int write_inter_picture(const char *who, int nal_type, int poc, int poc_l
     if (row_bytes[r] > longest) longest = row_bytes[r];
   }
   nal_writer w = {out, cap, 0, 0, 0, 0};
-  w.start(nal_type, true);           // the first NAL unit of its access unit: long start code; temporal id 0
+  bool first_nal = true;             // the first NAL unit of its access unit: long start code; temporal id 0
+  if (alf) write_alf_apss(w, *alf, aps, n_aps, first_nal);
+  w.start(nal_type, first_nal);
   w.bits(1, 1);                      // sh_picture_header_in_slice_header_flag
   w.bits(0, 1);                      // ph_gdr_or_irap_pic_flag
   w.bits(0, 1);                      // ph_non_ref_pic_flag
@@ -338,6 +372,7 @@ static int write_inter_picture(const char *who, int nal_type, int poc, int poc_l
   w.bits(0, 1);                      // ph_mvd_l1_zero_flag
   w.ue((uint32_t)slice_type);        // sh_slice_type
   if (nal_type == NAL_CRA) w.bits(0, 1);             // sh_no_output_of_prior_pics_flag (:1278)
+  if (alf) write_alf_slice_fields(w, *alf);
   const int lists = 1 + (copy_rpl1 ? 1 : 0);
   for (int list = 0; list < lists; ++list) {
     w.ue((uint32_t)n_ref_neg);       // num_ref_entries[0]
@@ -372,7 +407,7 @@ static int write_inter_picture(const char *who, int nal_type, int poc, int poc_l
   if (sao) w.bits(3, 2);             // sh_sao_luma_used_flag, sh_sao_chroma_used_flag
   finish_picture(w, out, cap, rows, row_pitch, row_bytes, n_rows, longest, checksum);
   *len = w.n;
-  if (w.n > cap) return uvghip_set_error(hipErrorInvalidValue, "uvghip_write_picture_nals_pb / _ra: the output buffer is too small (see *len)");
+  if (w.n > cap) return uvghip_set_error(hipErrorInvalidValue, alf ? "uvghip_write_picture_nals_gop_alf: the output buffer is too small (see *len)" : "uvghip_write_picture_nals_pb / _ra: the output buffer is too small (see *len)");
   return 0;
 }
 
@@ -406,4 +441,21 @@ extern "C" int uvghip_write_picture_nals_gop(int nal_type, int poc, int poc_lsb_
 {
   return write_inter_picture(__func__, nal_type, poc, poc_lsb_bits, slice_type, n_ref_neg, delta_neg, n_ref_pos, delta_pos, 0, tmvp, qp_delta, sao, rows, row_pitch, row_bytes, n_rows,
                              checksum, out, cap, len);
+}
+
+// ... of a picture of an --alf on / --alf full stream with a GOP structure: the APS NAL units in front of the slice and the slice header's ALF
+// fields between sh_slice_type / sh_no_output_of_prior_pics_flag and the reference picture lists (encoder_state-bitstream.c:1283-1330).
+// nal_type 7 / 8: an IDR picture (no lists; the POC in poc_lsb_bits bits).  Host function.
+extern "C" int uvghip_write_picture_nals_gop_alf(int nal_type, int poc, int poc_lsb_bits, int slice_type, int n_ref_neg, const int32_t *delta_neg, int n_ref_pos,
+                                                 const int32_t *delta_pos, int copy_rpl1, int tmvp, int qp_delta, int sao, const uvghip_alf_slice_t *alf,
+                                                 const uvghip_alf_aps_t *aps, int n_aps, const uint8_t *rows, size_t row_pitch, const int32_t *row_bytes, int n_rows,
+                                                 const uint32_t *checksum, uint8_t *out, size_t cap, size_t *len)
+{
+  if (nal_type == NAL_IDR_W_RADL || nal_type == NAL_IDR_N_LP) {
+    if (slice_type != 2 || n_ref_neg || n_ref_pos) return uvghip_set_error(hipErrorInvalidValue, "uvghip_write_picture_nals_gop_alf: an IDR picture is an I slice without reference picture lists");
+    return write_idr_picture_alf(__func__, nal_type, poc, poc_lsb_bits, qp_delta, sao, alf, aps, n_aps, rows, row_pitch, row_bytes, n_rows, checksum, out, cap, len);
+  }
+  if (int rc = check_alf_args(__func__, alf, aps, n_aps)) return rc;
+  return write_inter_picture(__func__, nal_type, poc, poc_lsb_bits, slice_type, n_ref_neg, delta_neg, n_ref_pos, delta_pos, copy_rpl1 != 0, tmvp, qp_delta, sao, rows, row_pitch, row_bytes,
+                             n_rows, checksum, out, cap, len, alf, aps, n_aps);
 }

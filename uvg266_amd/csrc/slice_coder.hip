@@ -350,7 +350,7 @@ struct pb_dev {
   const int32_t *col;
   const uvghip_inter4_t *inter4;
   const uint32_t *models_inter;
-  int32_t col_stride, pad;
+  int32_t col_stride, second_pass;     // second_pass: uvghip_slice_pb_t::second_pass
 };
 
 // uvg_hmvp_add_mv (src/inter.c:1831-1905) on the row's table: [0] size, then five units, most recent first
@@ -540,7 +540,7 @@ __device__ inline void alf_ctu(coder &c, row_state *R, const alf_dev &A, int k, 
     const uint8_t *en = A.flags + (size_t)comp * n;
     if (A.enabled[comp]) bin(MA + comp * 3 + (left >= 0 && en[left]) + (above >= 0 && en[above]), en[k]);      // code_alf_ctu_enable_flag (:1147)
     if (comp == 0) {
-      if (en[k] && A.enabled[0]) {                                             // code_alf_ctu_filter_index (:1209)
+      if (A.enabled[0] && en[k]) {                                             // code_alf_ctu_filter_index (:1209; a slice with ALF off may come without flags)
         const unsigned set = (unsigned)A.set_idx[k], n_aps = (unsigned)A.n_luma_aps;
         unsigned sym = set, max_v = 16;
         bool coded = true;
@@ -577,7 +577,9 @@ __device__ inline void alf_ctu(coder &c, row_state *R, const alf_dev &A, int k, 
 // PERSIST: the launch is a capped number of waves that take row after row from a ticket counter -- row r of every picture, then row r + 1:
 // the order in which rows become codable behind a search that is still running (uvgi_encode_slice_rows_behind) -- instead of a
 // wave per row: a waiting wave holds 10 KB of LDS a search workgroup cannot use.
-template <bool PERSIST = false>
+// TWO_PASS: the instantiation of uvghip_encode_slice_rows_pb_alf, which can start a row's history table from a first pass (see `pass` below); the
+// others compile as if the pass loop were not there.
+template <bool PERSIST = false, bool TWO_PASS = false>
 __global__ void __launch_bounds__(64)
 slice_rows_kernel(const pic_dev *__restrict__ pics, const pb_dev *__restrict__ pbs, const int32_t *__restrict__ sao, const uint16_t *__restrict__ sao_models,
                   int W, int H, int qp, int bitdepth, uint8_t *__restrict__ out, int row_cap, int32_t *__restrict__ row_bytes, const alf_dev *__restrict__ alfs = nullptr,
@@ -611,17 +613,25 @@ slice_rows_kernel(const pic_dev *__restrict__ pics, const pb_dev *__restrict__ p
     if (lane0) wait_final(wait_flags + (size_t)pic * wc * hc + (size_t)(cy - 1) * wc);
     __syncthreads();
   }
+  // chain (uvghip_slice_pb_t::second_pass): the encoder codes a picture of an --alf run twice -- simulated behind every CTU's search, for real after
+  // the picture's ALF (encoderstate.c:856-860, 1043-1052) -- and clears a row's history table before the first pass only (:1021-1028): the
+  // bitstream's pass of a row starts from the table the row's first pass left, so its AMVP predictors, its mvd bins and the models behind them are
+  // not the first pass's, which is what the search handed over.  The row then derives its own start: from the slice's initial models it codes,
+  // into nothing, the first CTU of every row above (each behind a pass 0 over that row, which feeds the table with the row's CUs and codes
+  // nothing), as the ALF models' start is derived without it.
+  const bool chain = TWO_PASS && PB && PB->second_pass;
+  const bool from_init = cy == 0 || chain;
   // scans, window bytes, the row's start models
   for (int i = threadIdx.x; i < NMODELS; i += blockDim.x) {
     R->rate[i] = k_ctx_init[3][i];
-    if (cy == 0) models_init_one(R->models, i, init_qp, slice);
+    if (from_init) models_init_one(R->models, i, init_qp, slice);
     else R->models[i] = D.models[((size_t)((cy - 1) * wc) * 3 + 2) * NMODELS + i];
   }
   if (PB) {
     if (threadIdx.x < NM_INTER) {
       const int i = threadIdx.x;
       R->rate[MI + i] = k_ctx_init_inter[3][i];
-      if (cy == 0) {
+      if (from_init) {
         const int v = k_ctx_init_inter[slice][i];
         const int slope = (v >> 3) - 4, offset = ((v & 7) * 18) + 1;
         int s = ((slope * (init_qp - 16)) >> 1) + offset;
@@ -642,7 +652,7 @@ slice_rows_kernel(const pic_dev *__restrict__ pics, const pb_dev *__restrict__ p
   if (threadIdx.x < 2) {
     const int i = threadIdx.x;
     R->rate[NMODELS + i] = k_ctx_init_sao[3][i];
-    if (cy == 0 || !sao_models) {
+    if (from_init || !sao_models) {
       const int v = k_ctx_init_sao[slice][i];
       const int slope = (v >> 3) - 4, offset = ((v & 7) * 18) + 1;
       int s = ((slope * (init_qp - 16)) >> 1) + offset;
@@ -669,11 +679,18 @@ slice_rows_kernel(const pic_dev *__restrict__ pics, const pb_dev *__restrict__ p
       s = s < 1 ? 1 : (s > 127 ? 127 : s);
       R->models[MA + i] = (uint32_t)((s << 8) & 0x7fe0) | ((uint32_t)((s << 8) & 0x7ffe) << 16);
     }
-    for (int r = 0; r < cy; ++r) alf_ctu<false>(c, R, A, r * wc, wc, wc * hc);
+    if (!chain) for (int r = 0; r < cy; ++r) alf_ctu<false>(c, R, A, r * wc, wc, wc * hc);
   }
   const int max_off = (1 << ((bitdepth < 10 ? bitdepth : 10) - 5)) - 1;
-  for (int cx = 0; cx < wc; ++cx) {
-    const int k = cy * wc + cx, x0 = cx * 64, y0 = cy * 64;
+  for (int ry = chain ? 0 : cy; ry <= cy; ++ry) {
+  if (chain) {          // a row above: a coder of its own that writes nowhere
+    if (lane0) for (int i = 0; i < 41; ++i) Q->hmvp[i] = 0;
+    c.low = 0; c.range = 510; c.bits_left = 23; c.nbuf = 0; c.buffered = 0xff; c.n = 0; c.zeros = 0;
+    c.cap = ry == cy ? row_cap : 0;
+  }
+  for (int pass = chain ? 0 : 1; pass < 2; ++pass)
+  for (int cx = 0; cx < (pass == 1 && ry < cy ? 1 : wc); ++cx) {
+    const int k = ry * wc + cx, x0 = cx * 64, y0 = ry * 64;
     const int16_t *co = D.coeff + (size_t)k * 6144;
     if (wait_flags) { if (lane0) wait_final(wait_flags + (size_t)pic * wc * hc + k); }
     __syncthreads();
@@ -700,6 +717,19 @@ slice_rows_kernel(const pic_dev *__restrict__ pics, const pb_dev *__restrict__ p
     }
     if (PB && lane0) Q->tab[17 * 17].type = 0;                      // the CTU above right: not a candidate under WPP
     __syncthreads();
+    if (TWO_PASS && pass == 0) {
+      if (lane0)
+        for (int z = 0; z < 256; ++z) {
+          const int lx = z_to_xy(z) * 4, ly = z_to_xy(z >> 1) * 4, x = x0 + lx, y = y0 + ly;
+          if (x >= W || y >= H) continue;
+          const row_state::cui cu = cu_of(R, x0, y0, x, y);
+          const int n = 1 << cu.log2w;
+          if ((lx & (n - 1)) || (ly & (n - 1))) continue;
+          const int e = ((ly >> 2) + 1) * 17 + (lx >> 2) + 1;
+          if (Q->flags[e][0] || cu.type == 2) hmvp_push(Q->hmvp, Q->tab[e]);      // a skipped or inter CU, in coding order
+        }
+      continue;          // (the next CTU's units are loaded behind the barrier at the top of the loop)
+    }
     if (sao) {
       if (threadIdx.x < 34) R->sao_l[threadIdx.x] = __hip_atomic_load(sao + ((size_t)pic * wc * hc + k) * 34 + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __syncthreads();
@@ -707,7 +737,7 @@ slice_rows_kernel(const pic_dev *__restrict__ pics, const pb_dev *__restrict__ p
     if (lane0 && sao) {                                             // encode_sao
       const int32_t *l = R->sao_l, *ch = l + 17;
       if (cx > 0) enc_bin(c, R, NMODELS, l[3]);
-      if (cy > 0 && !l[3]) enc_bin(c, R, NMODELS, l[4]);
+      if (ry > 0 && !l[3]) enc_bin(c, R, NMODELS, l[4]);
       if (!l[3] && !l[4]) { code_sao_color(c, R, l, 0, max_off); code_sao_color(c, R, ch, 1, max_off); code_sao_color(c, R, ch, 2, max_off); }
     }
     if (lane0 && alfs) alf_ctu<true>(c, R, alfs[pic], k, wc, wc * hc);
@@ -853,6 +883,7 @@ slice_rows_kernel(const pic_dev *__restrict__ pics, const pb_dev *__restrict__ p
       }
     }
   }
+  }
   if (lane0) {
     // end_of_sub_stream_one_bit (uvg_cabac_encode_bin_trm(1)), uvg_cabac_finish, a one bit, zeros to the byte boundary
     c.range -= 2;
@@ -893,6 +924,11 @@ extern "C" size_t uvghip_slice_rows_alf_workspace_bytes(int n_pictures)
 extern "C" size_t uvghip_slice_rows_pb_workspace_bytes(int n_pictures)
 {
   return n_pictures > 0 ? uvgi_align_up((size_t)n_pictures * sizeof(pic_dev), 256) + (size_t)n_pictures * sizeof(pb_dev) : 0;
+}
+
+extern "C" size_t uvghip_slice_rows_pb_alf_workspace_bytes(int n_pictures)
+{
+  return n_pictures > 0 ? uvgi_align_up((size_t)n_pictures * sizeof(pic_dev), 256) + uvgi_align_up((size_t)n_pictures * sizeof(pb_dev), 256) + (size_t)n_pictures * sizeof(alf_dev) : 0;
 }
 
 int uvgi_slice_rows_prepare(const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, int n_pictures, void *workspace, bool ordered, hipStream_t st)
@@ -965,6 +1001,42 @@ int uvgi_encode_slice_rows_behind(int bitdepth, const uvghip_ctu_params_t *param
   UVGHIP_CHECK_LAUNCH();
 }
 
+namespace {
+// the host descriptors of a call -> the tables the kernel reads; `who`: the entry point, for the error text
+int alf_table(const char *who, const uvghip_slice_alf_t *alf, int n_pictures, std::vector<alf_dev> &ad)
+{
+  ad.resize(n_pictures);
+  for (int i = 0; i < n_pictures; ++i) {
+    const uvghip_slice_alf_t &q = alf[i];
+    if ((q.alf_type != 1 && q.alf_type != 2) || q.n_luma_aps < 0 || q.n_luma_aps > 8 || q.n_alternatives_chroma < 0 || q.n_alternatives_chroma > 8 || q.cc_filter_count[0] > 4 ||
+        q.cc_filter_count[1] > 4 || ((q.enabled[0] || q.cc_enabled[0] || q.cc_enabled[1]) && (!q.ctu_flags || !q.filter_set_idx)))
+      return uvghip_set_error(hipErrorInvalidValue, who);
+    alf_dev &d = ad[i];
+    d.alf_type = q.alf_type; d.n_luma_aps = q.n_luma_aps; d.n_alts = q.n_alternatives_chroma; d.flags = q.ctu_flags; d.set_idx = q.filter_set_idx;
+    for (int c = 0; c < 3; ++c) d.enabled[c] = q.enabled[c] != 0;
+    for (int c = 0; c < 2; ++c) { d.cc_enabled[c] = q.cc_enabled[c] != 0; d.cc_count[c] = q.cc_filter_count[c]; }
+  }
+  return 0;
+}
+
+int pb_table(const char *who, const uvghip_slice_pb_t *pb, int n_pictures, bool alf_run, std::vector<pb_dev> &pd)
+{
+  pd.resize(n_pictures);
+  for (int i = 0; i < n_pictures; ++i) {
+    const uvghip_slice_pb_t &q = pb[i];
+    if ((q.slice_type != 0 && q.slice_type != 1) || !q.inter4 || !q.models_inter || q.n_refs < 1 || q.n_refs > 16 || q.l_size[0] < 1 || q.l_size[0] > 8 ||
+        q.l_size[1] < 0 || q.l_size[1] > 8 || q.max_merge < 1 || q.max_merge > 6 || (q.tmvp && !q.col) || q.frame_qp < 0 || q.frame_qp > 63)
+      return uvghip_set_error(hipErrorInvalidValue, who);
+    pb_dev &d = pd[i];
+    d.slice_type = q.slice_type; d.poc = q.poc; d.n_refs = q.n_refs; d.tmvp = q.tmvp; d.max_merge = q.max_merge; d.merge_level = q.merge_level; d.frame_qp = q.frame_qp;
+    memcpy(d.ref_pocs, q.ref_pocs, sizeof d.ref_pocs); memcpy(d.l_size, q.l_size, sizeof d.l_size); memcpy(d.l, q.l, sizeof d.l);
+    d.col = q.col; d.inter4 = q.inter4; d.models_inter = q.models_inter; d.col_stride = q.col_stride;
+    d.second_pass = alf_run && q.second_pass;          // (the plain entry point codes once)
+  }
+  return 0;
+}
+}  // namespace
+
 // ... of pictures of an --alf on / --alf full run: the CTU-level ALF syntax between a CTU's SAO syntax and its coding tree.
 extern "C" int uvghip_encode_slice_rows_alf(int bitdepth, const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, const uvghip_slice_alf_t *alf, int n_pictures,
                                             const int32_t *sao_info, const uint16_t *sao_models, void *workspace, uint8_t *out, int row_cap, int32_t *row_bytes, void *stream)
@@ -977,17 +1049,8 @@ extern "C" int uvghip_encode_slice_rows_alf(int bitdepth, const uvghip_ctu_param
   if (W <= 0 || H <= 0 || (W & 7) || (H & 7) || params->qp < 0 || params->qp > 63) return uvghip_set_error(hipErrorInvalidValue, __func__);
   hipStream_t st = uvghip_stream(stream);
   if (int rc = uvgi_slice_rows_prepare(params, pictures, n_pictures, workspace, true, st)) return rc;
-  std::vector<alf_dev> ad(n_pictures);
-  for (int i = 0; i < n_pictures; ++i) {
-    const uvghip_slice_alf_t &q = alf[i];
-    if ((q.alf_type != 1 && q.alf_type != 2) || q.n_luma_aps < 0 || q.n_luma_aps > 8 || q.n_alternatives_chroma < 0 || q.n_alternatives_chroma > 8 || q.cc_filter_count[0] > 4 ||
-        q.cc_filter_count[1] > 4 || ((q.enabled[0] || q.cc_enabled[0] || q.cc_enabled[1]) && (!q.ctu_flags || !q.filter_set_idx)))
-      return uvghip_set_error(hipErrorInvalidValue, "uvghip_encode_slice_rows_alf: slice descriptor");
-    alf_dev &d = ad[i];
-    d.alf_type = q.alf_type; d.n_luma_aps = q.n_luma_aps; d.n_alts = q.n_alternatives_chroma; d.flags = q.ctu_flags; d.set_idx = q.filter_set_idx;
-    for (int c = 0; c < 3; ++c) d.enabled[c] = q.enabled[c] != 0;
-    for (int c = 0; c < 2; ++c) { d.cc_enabled[c] = q.cc_enabled[c] != 0; d.cc_count[c] = q.cc_filter_count[c]; }
-  }
+  std::vector<alf_dev> ad;
+  if (int rc = alf_table("uvghip_encode_slice_rows_alf: slice descriptor", alf, n_pictures, ad)) return rc;
   unsigned char *aw = static_cast<unsigned char *>(workspace) + uvgi_align_up((size_t)n_pictures * sizeof(pic_dev), 256);
   if (int rc = uvghip_upload_ordered(aw, ad.data(), ad.size() * sizeof(alf_dev), st)) return rc;
   slice_rows_kernel<false><<<n_pictures * hc, 64, 0, st>>>(static_cast<const pic_dev *>(workspace), nullptr, sao_info, sao_models, W, H, params->qp, bitdepth, out, row_cap, row_bytes,
@@ -1007,20 +1070,39 @@ extern "C" int uvghip_encode_slice_rows_pb(int bitdepth, const uvghip_ctu_params
   if (W <= 0 || H <= 0 || (W & 7) || (H & 7) || params->qp < 0 || params->qp > 63) return uvghip_set_error(hipErrorInvalidValue, __func__);
   hipStream_t st = uvghip_stream(stream);
   if (int rc = uvgi_slice_rows_prepare(params, pictures, n_pictures, workspace, true, st)) return rc;
-  std::vector<pb_dev> pd(n_pictures);
-  for (int i = 0; i < n_pictures; ++i) {
-    const uvghip_slice_pb_t &q = pb[i];
-    if ((q.slice_type != 0 && q.slice_type != 1) || !q.inter4 || !q.models_inter || q.n_refs < 1 || q.n_refs > 16 || q.l_size[0] < 1 || q.l_size[0] > 8 ||
-        q.l_size[1] < 0 || q.l_size[1] > 8 || q.max_merge < 1 || q.max_merge > 6 || (q.tmvp && !q.col) || q.frame_qp < 0 || q.frame_qp > 63)
-      return uvghip_set_error(hipErrorInvalidValue, "uvghip_encode_slice_rows_pb: slice descriptor");
-    pb_dev &d = pd[i];
-    d.slice_type = q.slice_type; d.poc = q.poc; d.n_refs = q.n_refs; d.tmvp = q.tmvp; d.max_merge = q.max_merge; d.merge_level = q.merge_level; d.frame_qp = q.frame_qp;
-    memcpy(d.ref_pocs, q.ref_pocs, sizeof d.ref_pocs); memcpy(d.l_size, q.l_size, sizeof d.l_size); memcpy(d.l, q.l, sizeof d.l);
-    d.col = q.col; d.inter4 = q.inter4; d.models_inter = q.models_inter; d.col_stride = q.col_stride; d.pad = 0;
-  }
+  std::vector<pb_dev> pd;
+  if (int rc = pb_table("uvghip_encode_slice_rows_pb: slice descriptor", pb, n_pictures, false, pd)) return rc;
   unsigned char *pbw = static_cast<unsigned char *>(workspace) + uvgi_align_up((size_t)n_pictures * sizeof(pic_dev), 256);
   if (int rc = uvghip_upload_ordered(pbw, pd.data(), pd.size() * sizeof(pb_dev), st)) return rc;
   slice_rows_kernel<false><<<n_pictures * hc, 64, sizeof(row_state_pb), st>>>(static_cast<const pic_dev *>(workspace), reinterpret_cast<const pb_dev *>(pbw), sao_info, sao_models,
                                                                        W, H, params->qp, bitdepth, out, row_cap, row_bytes);
+  UVGHIP_CHECK_LAUNCH();
+}
+
+// P / B pictures of an --alf on / --alf full run: both tables.  The launch is uvghip_encode_slice_rows_pb's (row_state_pb in dynamic LDS) with the
+// ALF table beside it: a row's lane 0 initialises the ALF models for the slice type and walks the first CTUs of the rows above through them
+// before it codes.
+extern "C" int uvghip_encode_slice_rows_pb_alf(int bitdepth, const uvghip_ctu_params_t *params, const uvghip_ctu_picture_t *pictures, const uvghip_slice_pb_t *pb,
+                                               const uvghip_slice_alf_t *alf, int n_pictures, const int32_t *sao_info, const uint16_t *sao_models, void *workspace, uint8_t *out,
+                                               int row_cap, int32_t *row_bytes, void *stream)
+{
+  UVGHIP_REQUIRE_READY();
+  UVGHIP_REQUIRE_DEPTH(bitdepth);
+  if (!params || !pictures || !pb || !alf || n_pictures <= 0 || !workspace || !out || row_cap <= 0 || !row_bytes || (sao_info && !sao_models))
+    return uvghip_set_error(hipErrorInvalidValue, __func__);
+  const int W = params->pic_w, H = params->pic_h, hc = (H + 63) / 64;
+  if (W <= 0 || H <= 0 || (W & 7) || (H & 7) || params->qp < 0 || params->qp > 63) return uvghip_set_error(hipErrorInvalidValue, __func__);
+  hipStream_t st = uvghip_stream(stream);
+  std::vector<pb_dev> pd;
+  std::vector<alf_dev> ad;
+  if (int rc = pb_table("uvghip_encode_slice_rows_pb_alf: slice descriptor (P / B)", pb, n_pictures, true, pd)) return rc;
+  if (int rc = alf_table("uvghip_encode_slice_rows_pb_alf: slice descriptor (ALF)", alf, n_pictures, ad)) return rc;
+  if (int rc = uvgi_slice_rows_prepare(params, pictures, n_pictures, workspace, true, st)) return rc;
+  unsigned char *pbw = static_cast<unsigned char *>(workspace) + uvgi_align_up((size_t)n_pictures * sizeof(pic_dev), 256);
+  unsigned char *aw = pbw + uvgi_align_up((size_t)n_pictures * sizeof(pb_dev), 256);
+  if (int rc = uvghip_upload_ordered(pbw, pd.data(), pd.size() * sizeof(pb_dev), st)) return rc;
+  if (int rc = uvghip_upload_ordered(aw, ad.data(), ad.size() * sizeof(alf_dev), st)) return rc;
+  slice_rows_kernel<false, true><<<n_pictures * hc, 64, sizeof(row_state_pb), st>>>(static_cast<const pic_dev *>(workspace), reinterpret_cast<const pb_dev *>(pbw), sao_info,
+                                                                             sao_models, W, H, params->qp, bitdepth, out, row_cap, row_bytes, reinterpret_cast<const alf_dev *>(aw));
   UVGHIP_CHECK_LAUNCH();
 }

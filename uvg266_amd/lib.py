@@ -77,7 +77,7 @@ class SlicePb(ctypes.Structure):
     _fields_ = [("slice_type", ctypes.c_int32), ("poc", ctypes.c_int32), ("n_refs", ctypes.c_int32), ("ref_pocs", ctypes.c_int32 * 16),
                 ("l_size", ctypes.c_int32 * 2), ("l", (ctypes.c_int32 * 16) * 2), ("tmvp", ctypes.c_int32), ("max_merge", ctypes.c_int32),
                 ("merge_level", ctypes.c_int32), ("frame_qp", ctypes.c_int32), ("col", ctypes.c_void_p), ("inter4", ctypes.c_void_p),
-                ("models_inter", ctypes.c_void_p), ("col_stride", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+                ("models_inter", ctypes.c_void_p), ("col_stride", ctypes.c_int32), ("second_pass", ctypes.c_int32)]
 
 
 class CtuPbPicture(ctypes.Structure):
@@ -297,6 +297,12 @@ SIGNATURES = {
     "uvghip_write_picture_nals_gop": (c_int, [c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, ctypes.c_size_t, c_vp, c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "uvghip_write_idr_nals_ra": (c_int, [c_int, c_int, c_int, c_int, c_vp, ctypes.c_size_t, c_vp, c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "uvghip_write_picture_nals_ra": (c_int, [c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, ctypes.c_size_t, c_vp, c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "uvghip_write_picture_nals_gop_alf": (c_int, [c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp, ctypes.c_size_t, c_vp, c_int, c_vp, c_vp,
+                                                  ctypes.c_size_t, c_vp]),
+    "uvghip_slice_rows_pb_alf_workspace_bytes": (ctypes.c_size_t, [c_int]),
+    "uvghip_encode_slice_rows_pb_alf": (c_int, [c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
+    "uvghip_loop_pb_alf_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
+    "uvghip_loop_pb_alf_stage": (c_int, [c_int, c_vp, c_int, c_int, c_vp, ALF_DECIDE_FN, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
     "uvghip_slice_rows_pb_workspace_bytes": (ctypes.c_size_t, [c_int]),
     "uvghip_encode_slice_rows_pb": (c_int, [c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
     "uvghip_ctu_search_pb_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
