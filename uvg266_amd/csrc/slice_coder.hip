@@ -10,7 +10,9 @@
 // A WPP row is one substream: its coder starts fresh (uvg_cabac_start) and its context models start from the models after the
 // first CTU of the row above -- which the search already returned per CTU (the third model set) and uvghip_sao_decide_pictures
 // returned for the two SAO models.  So rows are independent: one workgroup (one wave) per (picture, row).  Inside a row the coder is
-// a chain bin after bin; lane 0 walks it, the other lanes only help to stage a transform block's levels into LDS.
+// a chain bin after bin; lane 0 walks it.  The other lanes stage a transform block's levels into LDS and, per coefficient group, keep
+// the coefficient models in their registers and hand lane 0 the group's regular bins as bytes (code_coeffs): the range arithmetic is
+// what is left of such a bin on the coding lane.
 #include "uvghip_common.h"
 #include "ctu_core.h"
 #include "inter_cand_dev.h"
@@ -71,6 +73,7 @@ struct row_state {
   // ... by SCAN position, with the position's level in the low half: the coding lane reads one word per position, in the order it
   // visits them (the next one is in flight while the bins of this one are coded), instead of scan -> level, scan -> template
   uint32_t ci_pos[1024];
+  uint32_t sb[17];                     // code_coeffs: the regular bins of the group being coded, a byte each in coding order (at most 64; + the word read ahead)
   int32_t sao_l[34];                   // the CTU's SAO decision (fetched by the wave: a row that codes BEHIND the launch that decides it reads past the caches)
 };
 // P / B slices: the CTU's motion for the AMVP predictors (the table uvg_inter_get_mv_cand_cua reads of the picture's cu array), the row's
@@ -250,20 +253,64 @@ __device__ inline void code_mvd(coder &c, row_state *R, int mvd_hor, int mvd_ver
   }
 }
 
-// uvg_encode_coeff_nxn on the levels staged in R->lv (n x n, raster); lane 0
-__device__ __forceinline__ void code_coeffs(coder &c, row_state *R, int n, int color)
+// What the coding lane needs of a regular bin besides its own range and low, in a byte: the bin's model state BEFORE the bin as
+// (q >> 2) << 1 -- q the state folded to its less probable half, of which uvg_cabac_encode_bin uses the five bits q >> 2 -- with "the
+// bin is the less probable symbol" in bit 0.  idx: ctu::cb_idx(state, bin) = the 8-bit state << 1 | bin (a byte cannot hold that as it is).
+__device__ __forceinline__ uint32_t sb_of(uint32_t idx)
+{
+  const uint32_t state = idx >> 1, mps = state >> 7, q = mps ? state ^ 0xffu : state;
+  return (q >> 2) << 1 | ((idx & 1u) ^ mps);
+}
+// uvg_cabac_encode_bin on such a byte: the range arithmetic of enc_bin without the model (the sweep of code_coeffs stepped it)
+__device__ __forceinline__ void enc_sb(coder &c, uint32_t sb)
+{
+#if defined(SLC_EXP_NO_BINS)
+  c.low += sb; return;      // (timing experiment)
+#endif
+  const uint32_t lps = (((sb >> 1) * (c.range >> 5)) >> 1) + 4;          // (at most 31 * 15 / 2 + 4: the table's & 0xff takes nothing off)
+  c.range -= lps;
+  if (sb & 1u) {
+    const int nb = __clz((int)lps) - 23;
+    c.low = (c.low + c.range) << nb;
+    c.range = lps << nb;
+    c.bits_left -= nb;
+    if (c.bits_left < 12) cwrite(c);
+  } else if (c.range < 256) {
+    c.low <<= 1; c.range <<= 1; c.bits_left--;
+    if (c.bits_left < 12) cwrite(c);
+  }
+}
+__device__ __forceinline__ unsigned long long uniform64(unsigned long long v)
+{
+  return (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32 | (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+
+// uvg_encode_coeff_nxn on the block stage() prepared (n x n); ALL 64 lanes call it, `c` means something in lane 0 only.
+// The coefficient models of the block -- sig, greater-1, parity, greater-2 -- live in lanes' registers as ctu::coeff_bits keeps them
+// (a lane per model; luma's greater-2 models a second one in the lanes 0..20), loaded when the block begins and written back when it
+// ends; nothing else touches them in between (the last-position prefix and the group flags are other models: enc_bin, lane 0).
+// Per coded group the two phases alternate -- one wave runs both either way, so a sweep over the whole block in front of one walk
+// would overlap nothing and would have to park a state per bin:
+// * all lanes: the sixteen lanes that hold the group's ci_pos words decide which positions the regular-bin budget still reaches (ballots
+//   over what each position spends) and form the key word per position; sixteen unrolled steps on v_readlane, in each the lane that
+//   owns a bin's model writes the bin's byte (sb_of) to its slot of R->sb -- the bins of the group in coding order -- and every model
+//   steps (cb_step);
+// * lane 0: the group's bytes through enc_sb, then the remainders, the bypass-coded positions and the signs.
+__device__ __forceinline__ void code_coeffs(coder &c, row_state *R, int n_, int color_)
 {
 #if defined(SLC_EXP_NO_COEFF)
   return;      // (timing experiment: tools/dev/coder_time.py)
 #endif
+  const int lane = threadIdx.x, l15 = lane & 15;
+  const bool lane0 = lane == 0;
+  const int n = __builtin_amdgcn_readfirstlane(n_), color = __builtin_amdgcn_readfirstlane(color_);      // (the same in every lane)
   const int l2 = ilog2_dev(n), nn = n * n, cgw = n >> 2, t = color ? 1 : 0;
   const uint16_t *scan = k_scan.v + scan_base(l2);
-  const int last = R->ci_last;                         // (stage() looked at the whole block with all lanes)
+  const int last = __builtin_amdgcn_readfirstlane(R->ci_last);                         // (stage() looked at the whole block with all lanes)
   if (last < 0) return;
-  const unsigned long long sig_cg = R->ci_cg, sig_r = R->ci_r;      // per group, by scan index / by raster position: has a level
-  (void)nn;
+  const unsigned long long sig_cg = uniform64(R->ci_cg), sig_r = uniform64(R->ci_r);      // per group, by scan index / by raster position: has a level
   const int cg_last = last >> 4;
-  {   // uvg_encode_last_significant_xy
+  if (lane0) {   // uvg_encode_last_significant_xy
     const int pos_last = scan[last], last_y = pos_last >> l2, last_x = pos_last - (last_y << l2);
     const int off = t ? 0 : (l2 == 2 ? 0 : l2 == 3 ? 3 : l2 == 4 ? 6 : 10);          // prefix_ctx[log2 size]
     const int sh = t ? clampi(n >> 3, 0, 2) : ((l2 + 1) >> 2);
@@ -279,7 +326,23 @@ __device__ __forceinline__ void code_coeffs(coder &c, row_state *R, int n, int c
     if (gx > 3) enc_eps(c, (uint32_t)(last_x - ((2 + (gx & 1)) << ((gx >> 1) - 1))), (gx - 2) / 2);
     if (gy > 3) enc_eps(c, (uint32_t)(last_y - ((2 + (gy & 1)) << ((gy >> 1) - 1))), (gy - 2) / 2);
   }
-  int reg_bins = (nn * 28) >> 4;
+  // the sweep's models (the lanes of ctu::coeff_bits): role 0 sig, 1 greater-1, 2 parity, 3 greater-2 (chroma), model k of the role
+  int role = -1, k = 0;
+  if (t) { if (lane < 8) { role = 0; k = lane; } else if (lane < 41) { role = 1 + (lane - 8) / 11; k = (lane - 8) % 11; } }
+  else { if (lane < 12) { role = 0; k = lane; } else if (lane < 33) { role = 1; k = lane - 12; } else if (lane < 54) { role = 2; k = lane - 33; } }
+  const bool luma = t == 0, two = luma && lane < 21;
+  const int model = role < 0 ? 0 : (role == 0 ? M_SIG + 12 * t : role == 1 ? M_GT1 + 21 * t : role == 2 ? M_PAR + 21 * t : M_GT2 + 21 * t) + k;
+  const int model2 = M_GT2 + (two ? lane : 0);
+  uint32_t st = R->models[model], st2 = R->models[model2];
+  const int rw = R->rate[model], rw2 = R->rate[model2];
+  const uint32_t rpk = cb_rpk(rw), addpk = cb_addpk(rw), rpk2 = cb_rpk(rw2), addpk2 = cb_addpk(rw2);
+  const uint32_t kGate = 0x7ffe7fe0u;
+  // a position's key: a byte per role, context << 1 | bin, 0xff where it codes no such bin; a lane's model codes the bin where the byte
+  // of its role is 2 k or 2 k + 1.  A bin's slot: the bins of the group so far + its rank in its position (sig, greater-1, parity, greater-2)
+  const uint32_t sh8 = role < 0 ? 0u : (uint32_t)role * 8u, k2 = role < 0 ? 0x1000u : (uint32_t)k << 1, l2k = two ? (uint32_t)lane << 1 : 0x1000u;
+  const int rk = role < 1 ? 0 : role - 1;
+  uint8_t *const sbb = reinterpret_cast<uint8_t *>(R->sb);
+  int reg_bins = (nn * 28) >> 4;                       // the block's budget of regular bins: the same in every lane
   // the groups' positions in the block: group g of the scan sits at the 4x4 whose first coefficient is scan[g * 16]
   for (int g = cg_last; g >= 0; --g) {
     const int first = scan[g * 16];
@@ -289,58 +352,90 @@ __device__ __forceinline__ void code_coeffs(coder &c, row_state *R, int n, int c
     else {
       const int right = cx + 1 < cgw ? (int)((sig_r >> (cy * cgw + cx + 1)) & 1) : 0;
       const int lower = cy + 1 < cgw ? (int)((sig_r >> ((cy + 1) * cgw + cx)) & 1) : 0;
-      enc_bin(c, R, M_SIGGRP + 2 * t + ((right || lower) ? 1 : 0), sig);
+      if (lane0) enc_bin(c, R, M_SIGGRP + 2 * t + ((right || lower) ? 1 : 0), sig);
     }
     if (!sig) continue;
     const int min_sub = g << 4;
-    const int first_sig = (g == cg_last) ? last : (min_sub + 15);
-    const int infer_sig = (first_sig != last) ? ((g != 0) ? min_sub : -1) : first_sig;
-    int num_nz = 0, next_sig;
-    uint32_t signs = 0;
-    uint32_t ahead = R->ci_pos[first_sig];
-    for (next_sig = first_sig; next_sig >= min_sub && reg_bins >= 4; next_sig--) {
-      const uint32_t w = ahead;                            // (stage(): the position's level and context template, all lanes)
-      if (next_sig > 0) ahead = R->ci_pos[next_sig - 1];
-      const int level = (int)(int16_t)(w & 0xffffu), rec = (int)(w >> 16);
-      const int s = level != 0;
-      if (num_nz || next_sig != infer_sig) {
-        enc_bin(c, R, M_SIG + 12 * t + (rec & 15), s);
-        reg_bins--;
+    const int top = g == cg_last ? last - min_sub : 15;          // the group's first position in coding order
+    // ---- all lanes: the lanes 0..15 hold the group's positions (stage(): level and context template) ----
+    const uint32_t w = R->ci_pos[min_sub + l15];                  // (behind the last position: never written, masked by `pos`)
+    const bool pos = lane < 16 && l15 <= top, at_last = min_sub + l15 == last;
+    const int level = (int)(int16_t)(w & 0xffffu);
+    const uint32_t a = pos ? (uint32_t)iabs_(level) : 0u, rec = w >> 16;
+    const uint32_t nzm = (uint32_t)__ballot(a != 0), negm = (uint32_t)__ballot(pos && level < 0);
+    // the sig flag is not coded at the block's last position, nor at the first scan position of a group between the ends whose other fifteen are zero
+    const bool sig_coded = pos && !at_last && !(l15 == 0 && g != 0 && g != cg_last && !(nzm >> 1));
+    const uint32_t spend = (sig_coded ? 1u : 0u) + (a ? 1u + (a > 1 ? 2u : 0u) : 0u);
+    // a position is regular while the budget less what the positions before it in coding order (the lanes above it) spent is at least 4
+    const uint32_t b0 = (uint32_t)__ballot(spend & 1u), b1 = (uint32_t)__ballot(spend & 2u), b2 = (uint32_t)__ballot(spend & 4u);
+    const uint32_t above = 0xfffeu << l15;
+    const int before = __popc(b0 & above) + 2 * __popc(b1 & above) + 4 * __popc(b2 & above);
+    const bool regular = pos && reg_bins - before >= 4;
+    const uint32_t regm = (uint32_t)__ballot(regular);          // (the positions top .. next_sig + 1 of the group)
+    const int next_sig = min_sub + (regm ? __ffs((int)regm) - 2 : top);
+    const uint32_t remm = (uint32_t)__ballot(regular && a >= 4);
+    reg_bins -= __popc(b0 & regm) + 2 * __popc(b1 & regm) + 4 * __popc(b2 & regm);
+    // (the block's last position is coded before any template was looked at: offset 0, encode_coding_tree-generic.c:203-215)
+    const uint32_t of2 = at_last ? 0u : ((rec >> 4) & 31u) << 1;
+    uint32_t keys = (sig_coded ? (rec & 15u) << 1 | (a != 0 ? 1u : 0u) : 0xffu) | (a != 0 ? of2 | (a > 1 ? 1u : 0u) : 0xffu) << 8 |
+                    (a > 1 ? of2 | (a & 1u) : 0xffu) << 16 | (a > 1 ? of2 | (a >= 4 ? 1u : 0u) : 0xffu) << 24;
+    if (!regular) keys = 0xffffffffu;                             // behind the budget's end: no regular bin, the models do not step
+    int cnt = 0;                                                  // the group's regular bins so far (the keys are in SGPRs: wave-uniform)
+#pragma unroll
+    for (int j = 15; j >= 0; --j) {
+      const uint32_t kj = (uint32_t)__builtin_amdgcn_readlane((int)keys, j);
+      if (kj == 0xffffffffu) continue;
+      const int hs = (kj & 0xffu) != 0xffu, h1 = ((kj >> 8) & 0xffu) != 0xffu, h2 = (kj >> 24) != 0xffu;
+      const uint32_t d = ((kj >> sh8) & 0xffu) - k2;
+      if (d < 2u) sbb[cnt + rk + (role > 0 ? hs : 0)] = (uint8_t)sb_of(cb_idx(st, d == 1u));
+      st = cb_step(st, rpk, d < 2u ? kGate : 0u, d == 1u ? addpk : 0u);
+      if (luma && h2) {                                           // (wave-uniform: the position codes a greater-2 bin)
+        const uint32_t d2 = (kj >> 24) - l2k;
+        if (d2 < 2u) sbb[cnt + hs + 2] = (uint8_t)sb_of(cb_idx(st2, d2 == 1u));
+        st2 = cb_step(st2, rpk2, d2 < 2u ? kGate : 0u, d2 == 1u ? addpk2 : 0u);
       }
-      if (s) {
-        num_nz++;
-        signs = (signs << 1) | (level < 0);
-        // (the block's last position is coded before any template was looked at: offset 0, encode_coding_tree-generic.c:203-215)
-        const int ofs = next_sig == last ? 0 : (rec >> 4) & 31;
-        int rem = iabs_(level) - 1;
-        const int gt1 = rem ? 1 : 0;
-        enc_bin(c, R, M_GT1 + 21 * t + ofs, gt1);
-        reg_bins--;
-        if (gt1) {
-          rem -= 1;
-          enc_bin(c, R, M_PAR + 21 * t + ofs, rem & 1);
-          rem >>= 1;
-          reg_bins--;
-          enc_bin(c, R, M_GT2 + 21 * t + ofs, rem ? 1 : 0);
-          reg_bins--;
-        }
+      cnt += hs + h1 + 2 * h2;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");        // (one wave: its LDS accesses execute in order; this orders the compiler)
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // ---- lane 0: the coder ----
+    if (lane0) {
+      const uint32_t *const sbw = R->sb;
+      uint32_t ahead = sbw[0];
+      for (int i = 0; i < cnt; i += 4) {                          // four bins a word, the next word in flight
+        uint32_t cur = ahead;
+        ahead = sbw[(i >> 2) + 1];
+        const int m = cnt - i < 4 ? cnt - i : 4;
+#pragma unroll 1
+        for (int q = 0; q < m; ++q) { enc_sb(c, cur & 0xffu); cur >>= 8; }
       }
+      for (uint32_t rm = remm; rm;) {                             // Golomb-Rice remainders of the context-coded positions
+        const int j = 31 - __clz((int)rm);
+        rm &= ~(1u << j);
+        const uint32_t wj = R->ci_pos[min_sub + j];
+        const uint32_t aj = (uint32_t)iabs_((int)(int16_t)(wj & 0xffffu));
+        enc_remain(c, (aj - 4) >> 1, (wj >> (16 + 9)) & 3);
+      }
+      for (int sp = next_sig; sp >= min_sub; sp--) {               // positions coded in bypass once the regular bins are spent
+        const uint32_t wj = R->ci_pos[sp];
+        const uint32_t aj = (uint32_t)iabs_((int)(int16_t)(wj & 0xffffu));
+        const uint32_t rice = (wj >> (16 + 11)) & 3, pos0 = 1u << rice;
+        enc_remain(c, aj == 0 ? pos0 : (aj <= pos0 ? aj - 1 : aj), rice);
+      }
+      uint32_t signs = 0;                                          // the signs of the group's levels, in coding order
+      for (uint32_t nz = nzm; nz;) {
+        const int j = 31 - __clz((int)nz);
+        nz &= ~(1u << j);
+        signs = (signs << 1) | ((negm >> j) & 1u);
+      }
+      enc_eps(c, signs, __popc(nzm));
     }
-    for (int sp = first_sig; sp > next_sig; sp--) {               // Golomb-Rice remainders of the context-coded positions
-      const uint32_t w = R->ci_pos[sp];
-      const uint32_t a = (uint32_t)iabs_((int)(int16_t)(w & 0xffffu));
-      if (a >= 4) enc_remain(c, (a - 4) >> 1, (w >> (16 + 9)) & 3);
-    }
-    for (int sp = next_sig; sp >= min_sub; sp--) {                 // positions coded in bypass once the regular bins are spent
-      const uint32_t w = R->ci_pos[sp];
-      const int level = (int)(int16_t)(w & 0xffffu);
-      const uint32_t a = (uint32_t)iabs_(level);
-      const uint32_t rice = (w >> (16 + 11)) & 3, pos0 = 1u << rice;
-      enc_remain(c, a == 0 ? pos0 : (a <= pos0 ? a - 1 : a), rice);
-      if (a) { num_nz++; signs = (signs << 1) | (level < 0); }
-    }
-    enc_eps(c, signs, num_nz);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");        // (the next group's bytes go where lane 0 has just read)
+    __builtin_amdgcn_wave_barrier();
   }
+  if (role >= 0) R->models[model] = st;
+  if (two) R->models[model2] = st2;
 }
 
 struct pic_dev { const uvghip_scu_t *cu; const int16_t *coeff; const uint32_t *models; int cu_stride, pad; };
@@ -580,7 +675,7 @@ __device__ inline void alf_ctu(coder &c, row_state *R, const alf_dev &A, int k, 
 // TWO_PASS: the instantiation of uvghip_encode_slice_rows_pb_alf, which can start a row's history table from a first pass (see `pass` below); the
 // others compile as if the pass loop were not there.
 template <bool PERSIST = false, bool TWO_PASS = false>
-__global__ void __launch_bounds__(64)
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4)))          // (at most 128 VGPRs: four waves a SIMD, as many rows as the LDS lets in)
 slice_rows_kernel(const pic_dev *__restrict__ pics, const pb_dev *__restrict__ pbs, const int32_t *__restrict__ sao, const uint16_t *__restrict__ sao_models,
                   int W, int H, int qp, int bitdepth, uint8_t *__restrict__ out, int row_cap, int32_t *__restrict__ row_bytes, const alf_dev *__restrict__ alfs = nullptr,
                   const int32_t *wait_flags = nullptr, int32_t *ticket = nullptr, int n_pictures = 0, int row0 = 0, int n_rows = 0)
@@ -846,9 +941,9 @@ slice_rows_kernel(const pic_dev *__restrict__ pics, const pb_dev *__restrict__ p
                 enc_bin(c, R, M_CBF_CB, cb_u); enc_bin(c, R, M_CBF_CR + cb_u, cb_v);
                 if (n == 64 || cb_u || cb_v) enc_bin(c, R, M_CBF_LUMA, cb_y);       // otherwise inferred 1 (:705-716)
               }
-              if (cb_y) { stage(R, co + tly * 64 + tlx, 64, tn, 0); if (lane0) code_coeffs(c, R, tn, 0); }
-              if (cb_u) { stage(R, co + 4096 + (tly >> 1) * 32 + (tlx >> 1), 32, tn >> 1, 1); if (lane0) code_coeffs(c, R, tn >> 1, 1); }
-              if (cb_v) { stage(R, co + 5120 + (tly >> 1) * 32 + (tlx >> 1), 32, tn >> 1, 2); if (lane0) code_coeffs(c, R, tn >> 1, 2); }
+              if (cb_y) { stage(R, co + tly * 64 + tlx, 64, tn, 0); code_coeffs(c, R, tn, 0); }
+              if (cb_u) { stage(R, co + 4096 + (tly >> 1) * 32 + (tlx >> 1), 32, tn >> 1, 1); code_coeffs(c, R, tn >> 1, 1); }
+              if (cb_v) { stage(R, co + 5120 + (tly >> 1) * 32 + (tlx >> 1), 32, tn >> 1, 2); code_coeffs(c, R, tn >> 1, 2); }
             }
           }
           continue;
@@ -867,18 +962,18 @@ slice_rows_kernel(const pic_dev *__restrict__ pics, const pb_dev *__restrict__ p
           if (!sep) { enc_bin(c, R, M_CBF_CB, cb_u); enc_bin(c, R, M_CBF_CR + cb_u, cb_v); }
           enc_bin(c, R, M_CBF_LUMA, cb_y);
         }
-        if (cb_y) { stage(R, co + tly * 64 + tlx, 64, tn, 0); if (lane0) code_coeffs(c, R, tn, 0); }
+        if (cb_y) { stage(R, co + tly * 64 + tlx, 64, tn, 0); code_coeffs(c, R, tn, 0); }
         if (!sep) {
-          if (cb_u) { stage(R, co + 4096 + (tly >> 1) * 32 + (tlx >> 1), 32, tn >> 1, 1); if (lane0) code_coeffs(c, R, tn >> 1, 1); }
-          if (cb_v) { stage(R, co + 5120 + (tly >> 1) * 32 + (tlx >> 1), 32, tn >> 1, 2); if (lane0) code_coeffs(c, R, tn >> 1, 2); }
+          if (cb_u) { stage(R, co + 4096 + (tly >> 1) * 32 + (tlx >> 1), 32, tn >> 1, 1); code_coeffs(c, R, tn >> 1, 1); }
+          if (cb_v) { stage(R, co + 5120 + (tly >> 1) * 32 + (tlx >> 1), 32, tn >> 1, 2); code_coeffs(c, R, tn >> 1, 2); }
         } else if (last4) {
           // the 8x8 area's chroma after its last luma CU: mode (the co-located luma CU is this one), cbfs of the area's first entry, levels
           const int acbf = cu_of(R, x0, y0, x & ~7, y & ~7).cbf;
           const int au = (acbf >> 1) & 1, av = (acbf >> 2) & 1;
           if (lane0) { code_chroma_mode(c, R, mode_c, mode); enc_bin(c, R, M_CBF_CB, au); enc_bin(c, R, M_CBF_CR + au, av); }
           const int cbx = (lx & ~7) >> 1, cby = (ly & ~7) >> 1;
-          if (au) { stage(R, co + 4096 + cby * 32 + cbx, 32, 4, 1); if (lane0) code_coeffs(c, R, 4, 1); }
-          if (av) { stage(R, co + 5120 + cby * 32 + cbx, 32, 4, 2); if (lane0) code_coeffs(c, R, 4, 2); }
+          if (au) { stage(R, co + 4096 + cby * 32 + cbx, 32, 4, 1); code_coeffs(c, R, 4, 1); }
+          if (av) { stage(R, co + 5120 + cby * 32 + cbx, 32, 4, 2); code_coeffs(c, R, 4, 2); }
         }
       }
     }
