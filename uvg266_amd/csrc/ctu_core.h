@@ -1471,6 +1471,26 @@ CTU_DEV double rq_last_lower(double a, double b) { return b < a ? b : a; }
 // at_min: the candidates whose total equals the minimum m (bit k: position k of the group).  -> k + 1 of the winner, 0: best_cost stays
 CTU_DEV int rq_last_pick(double m, unsigned at_min, double best_cost) { return (m < best_cost && at_min) ? 32 - __builtin_clz(at_min) : 0; }
 
+// the level a position's fixed point STARTS from.  The fixed point does not depend on it (a decision reads only levels later in
+// scan order: after round k the last k positions of a pass hold the walk's values from any start), the number of rounds does: at
+// the QPs of real use RDOQ turns a large share of the candidates of 1 into 0, and a pass that starts from the candidates pays a
+// round that changes them and a round that confirms.  So a candidate of 1 starts at 0 where "not significant" is the cheaper of the
+// two under a neutral context -- the significance model of template sum class 1, the greater-1 model of template sum 0, regular
+// bins -- which is coded_level2's comparison with the squares taken apart:
+//   c0 + lambda sig.b0 <= (level_double - Q)^2 error_scale + lambda (32768 + gt1.b0) + lambda sig.b1,   Q = 1 << q_bits
+//   <=>  (2 level_double - Q) Q error_scale <= lambda (32768 + gt1.b0 + sig.b1 - sig.b0).
+// Every other candidate starts as itself.  Bit-exact with nothing: a wrong guess costs a round, never a level.
+CTU_DEV int rq_start_level(const rdoq_env &E, int color, int pos_x, int pos_y, int32_t level_double, int mal)
+{
+  const int diag = pos_x + pos_y;
+  const int ctx_sig = 1 + (diag < 2 ? 4 : 0) + ((color == 0 && diag < 5) ? 4 : 0);
+  const int ctx_set = 1 + (!diag ? ((color == 0) ? 15 : 5) : (color == 0) ? (diag < 3 ? 10 : (diag < 10 ? 5 : 0)) : 0);
+  const rq_pair sig = rbits2(M_SIG + (E.t ? 12 : 0) + ctx_sig), gt1 = rbits2(M_GT1 + (E.t ? 21 : 0) + ctx_set);
+  const double q = (double)(1 << E.q_bits);
+  const bool zero = ((double)level_double * 2.0 - q) * (q * E.error_scale) <= E.lambda * (double)(32768 + gt1.b0 + sig.b1 - sig.b0);
+  return (mal == 1 && zero) ? 0 : mal;
+}
+
 #if !defined(__HIPCC__)
 #include "ctu_rdoq_emul.h"
 #else
@@ -1480,8 +1500,10 @@ CTU_DEV int rq_last_pick(double m, unsigned at_min, double best_cost) { return (
 //   * the positions of a 4x4 group are decided together by 16 lanes, up to four groups of one diagonal of the group grid at a time
 //     (a group per row of lanes: see the loop).  A decision reads only levels of positions later in scan
 //     order (the context template looks right / down), so the group's decisions are the unique solution of a set of equations over
-//     a DAG: the lanes start from the candidates, re-decide against each other's current levels and stop when a round changes
-//     nothing -- at that point every position holds exactly what the reference's walk leaves there (<= 8 rounds, mostly 2).
+//     a DAG: the lanes start from a rate-aware guess (rq_start_level: a candidate of 1 that a neutral context would drop starts at
+//     0, every other one as itself; a pass without regular bins starts from the candidates), re-decide against each other's current
+//     levels and stop when a round changes nothing -- at that point every position holds exactly what the reference's walk leaves
+//     there, from any start; the start only sets the number of rounds (<= 8; from the candidates mostly 2, from the guess mostly 1).
 //     This needs the regular-bin budget not to run out inside the group (an upper bound from the candidates says so) or to have run
 //     out for good; the one or two groups where it does run out are walked position by position by lane 0;
 //   * the double-precision sums the reference forms in scan order (base cost, group statistics, the last-position search): every
@@ -1533,18 +1555,22 @@ template <typename PX> CTU_INLINE1 CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W
   const int32_t cap = 0x7fffffff - cap_half;
   RQ_T0(W)
   // ---- every position: candidate; the last candidate in scan order ----
-  int my_last = -1;
+  int my_last = -1, my_last_mal = 0;
   PAR_FOR(sp, nn) {
     const int blk = scan[sp];
     const int64_t prod = (int64_t)iabs_((int)coef[blk]) * E.q;
     const int32_t level_double = (int32_t)(prod < cap ? prod : cap);
     const int mal = (int)((uint32_t)(level_double + cap_half) >> E.q_bits);
-    dst[blk] = (int16_t)mal;
-    if (mal > 0 && sp > my_last) my_last = sp;
+    // (what the passes start from: rq_start_level)
+    dst[blk] = (int16_t)rq_start_level(E, color, blk & (n - 1), blk >> l2, level_double, mal);
+    if (mal > 0 && sp > my_last) { my_last = sp; my_last_mal = mal; }
     if (sp < 64) V->cg_flag[sp] = 0;
   }
+  const int own_last = my_last;
   for (int o = 32; o >= 1; o >>= 1) { const int v = __shfl_xor(my_last, o, 64); my_last = v > my_last ? v : my_last; }
   const int last_scanpos = my_last;
+  // the last candidate cannot become 0: it starts as itself (its lane stored the guess above: the same lane, the same address)
+  if (own_last >= 0 && own_last == last_scanpos) dst[scan[own_last]] = (int16_t)my_last_mal;
   CTU_SYNC();
   if (last_scanpos < 0) { if (CTU_TID == 0) V->rq_i[1] = 0; CTU_SYNC(); return; }
   RQ_T(12);
@@ -1632,7 +1658,12 @@ template <typename PX> CTU_INLINE1 CTU_DEV void rdoq_wave(lds<PX> *S, scratch *W
           const int nb = scan[scanpos + 1];
           go_rice = go_rice_par(template_abs_sum(coef, 4, nb & (n - 1), nb >> l2, n));      // sic: the INPUT coefficients (rdo.c:1697)
         }
+        // the start: dst holds rq_start_level's guess since the candidates' loop, and lev is what dst holds (read back: forming the
+        // guess again here costs the all-intra kernels 16 to 64 B of stack per lane, over the ceilings of tests/test_abi.py).  The
+        // guess prices regular bins: a pass behind the budget's end starts from the candidates, which go back into dst first.
         lev = mal0;
+        if (regular) lev = mine ? (int)dst[blk] : 0;
+        else { if (mine) dst[blk] = (int16_t)mal0; CTU_SYNC(); }
         for (;;) {                                  // (until no lane of any row changed)
           bool changed = false;
           RQ_N(12, 1)

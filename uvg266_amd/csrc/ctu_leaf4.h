@@ -706,7 +706,7 @@ template <typename PX> CTU_DEV int leaf_rdoq(lds<PX> *S, int coef, int color, in
     if (mine && sp != 15 && !is_last) go_rice_reg = nb;
   }
   // ---- the group's decisions: a fixed point over the DAG "later in scan order" ----
-  int lev = mine ? mal : 0;
+  int lev = mine ? (is_last ? mal : rq_start_level(E, color, px, py, level_double, mal)) : 0;          // (a start, not a decision: see rq_start_level)
   double cc = 0, cs = 0;
   for (;;) {
     const int l1 = lf_nb<1>(lev), l2 = lf_nb<2>(lev), l5 = lf_nb<5>(lev), l4 = lf_nb<4>(lev), l8 = lf_nb<8>(lev);
@@ -906,7 +906,7 @@ template <typename PX> CTU_DEV int leaf_rdoq_rows(lds<PX> *S, int coef, int colo
     if (mine && sp != 15 && !is_last) go_rice_reg = nb;
   }
   // ---- the groups' decisions: a fixed point over the DAG "later in scan order", all rows together ----
-  int lev = mine ? mal : 0;
+  int lev = mine ? (is_last ? mal : rq_start_level(E, color, px, py, level_double, mal)) : 0;          // (a start, not a decision: see rq_start_level)
   double cc = 0, cs = 0;
   for (;;) {
     const int l1 = lf_nb<1>(lev), l2 = lf_nb<2>(lev), l5 = lf_nb<5>(lev), l4 = lf_nb<4>(lev), l8 = lf_nb<8>(lev);

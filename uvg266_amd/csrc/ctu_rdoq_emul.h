@@ -3,6 +3,149 @@
 // This is the reference's walk, position by position; the device decides a group's positions by a fixed-point iteration over the
 // lanes' registers.  So the CPU tests hold the logic around RDOQ to the reference, and the GPU tests the device's formulation.
 #pragma once
+#if defined(CTU_RDOQ_START_STATS)
+// tests/test_rdoq_start.py only (the test builds tests/emul/ctu_emul.cpp with this macro; no other build defines it).  Beside the
+// walk, a plain transcription of the DEVICE's fixed point -- rdoq_wave's passes of up to four groups of a diagonal, the 4x4 leaf's one
+// group with every position's own "regular" -- run from four starts: the candidates, rq_start_level's guess as the device places
+// it, all zeros, and a seeded random start <= candidate.  Every start has to end at the walk's levels; the rounds are counted.
+// Index of a block's class: 2 * (log2 size - 2) + (chroma ? 1 : 0).
+struct rq_start_stats {
+  int64_t passes, rounds[4], mismatches, zero_kept1, one_took0, last_cand1, passes_of[3], slow_groups;
+};
+struct rq_start_pass {
+  int next_top, ng, on;                   // the group that opens the next pass; this pass's groups; decided by the fixed point
+  int16_t want[4][16];                    // its groups' levels as the iteration leaves them (row r: group top - r)
+};
+inline rq_start_stats g_rq_start[8];
+inline uint32_t g_rq_start_seed = 1;
+extern "C" __attribute__((visibility("default"), used)) inline void ctu_emul_rdoq_start_stats(int64_t *out, int reset)
+{
+  if (out) memcpy(out, g_rq_start, sizeof g_rq_start);
+  if (reset) { memset(g_rq_start, 0, sizeof g_rq_start); g_rq_start_seed = 1; }
+}
+struct rq_start_cand { int32_t level_double; int mal; };
+CTU_DEV rq_start_cand rq_start_candidate(const rdoq_env &E, int32_t q, int coef)
+{
+  const int cap_half = 1 << (E.q_bits - 1);
+  const int64_t prod = (int64_t)iabs_(coef) * q;
+  const int32_t cap = 0x7fffffff - cap_half;
+  rq_start_cand c;
+  c.level_double = (int32_t)(prod < cap ? prod : cap);
+  c.mal = (int)((uint32_t)(c.level_double + cap_half) >> E.q_bits);
+  return c;
+}
+// one group from one start, in place (the group's positions of dst are undecided: they are put back as they were).  pass_regular:
+// the pass's flag (n >= 8); n == 4: every position's own, from the bins the current levels later in scan order spend.
+// -> rounds, the confirming one included; lev_out: the levels at the fixed point; start_out: the start.
+inline int rq_start_iterate(const rdoq_env &E, int32_t q, const uint16_t *scan, const int16_t *coef, int16_t *dst, int n, int l2, int color, int cg,
+                            int last_scanpos, bool pass_regular, int start, int16_t *lev_out, int16_t *start_out)
+{
+  int16_t keep[16], lev[16], nxt[16];
+  for (int k = 0; k < 16; ++k) {
+    const int scanpos = cg * 16 + k, blk = scan[scanpos];
+    const rq_start_cand c = rq_start_candidate(E, q, coef[blk]);
+    const bool mine = scanpos <= last_scanpos, is_last = scanpos == last_scanpos;
+    keep[k] = dst[blk];
+    int s = c.mal;
+    if (start == 1) {
+      const int g = rq_start_level(E, color, blk & (n - 1), blk >> l2, c.level_double, c.mal);
+      s = (is_last || !(n == 4 || pass_regular)) ? c.mal : g;      // (rdoq_wave's pass without regular bins starts from the candidates)
+    }
+    if (start == 2) s = 0;
+    if (start == 3) { g_rq_start_seed = g_rq_start_seed * 1664525u + 1013904223u; s = (int)((g_rq_start_seed >> 8) % (uint32_t)(c.mal + 1)); }
+    lev[k] = (int16_t)(mine ? s : 0);
+    start_out[k] = lev[k];
+    dst[blk] = lev[k];
+  }
+  int rounds = 0;
+  for (;;) {
+    bool changed = false;
+    ++rounds;
+    for (int k = 0; k < 16; ++k) {
+      const int scanpos = cg * 16 + k, blk = scan[scanpos];
+      nxt[k] = lev[k];
+      if (scanpos > last_scanpos) continue;
+      const rq_start_cand c = rq_start_candidate(E, q, coef[blk]);
+      const bool is_last = scanpos == last_scanpos;
+      bool regular = pass_regular;
+      if (n == 4) {
+        int spent = 0;
+        for (int j = k + 1; j < 16 && j <= last_scanpos; ++j) spent += (lev[j] < 2 ? lev[j] : 3) + (j == last_scanpos ? 0 : 1);
+        regular = 28 - spent >= 4;
+      }
+      int go_rice = 0;
+      if (regular && k != 15 && !is_last) {
+        const int nb = scan[scanpos + 1];
+        go_rice = go_rice_par(template_abs_sum(coef, 4, nb & (n - 1), nb >> l2, n));
+      }
+      const double c0 = (double)c.level_double * (double)c.level_double * E.error_scale;
+      const rdoq_pos r = rdoq_decide_at(E, (const int16_t *)dst, n, color, blk & (n - 1), blk >> l2, is_last, regular, go_rice, c0, c.level_double, (uint32_t)c.mal);
+      nxt[k] = (int16_t)r.level;
+      changed |= nxt[k] != lev[k];
+    }
+    for (int k = 0; k < 16; ++k) { lev[k] = nxt[k]; dst[scan[cg * 16 + k]] = lev[k]; }
+    if (!changed || rounds > 64) break;
+  }
+  for (int k = 0; k < 16; ++k) { lev_out[k] = lev[k]; dst[scan[cg * 16 + k]] = keep[k]; }
+  return rounds;
+}
+// at a group the walk is about to enter: where it opens a pass, the pass as the device forms it
+inline void rq_start_open(rq_start_pass &HS, const rdoq_env &E, int32_t q, const uint16_t *scan, const int16_t *coef, int16_t *dst, int n, int l2, int color,
+                          int cgs, int last_scanpos, uint32_t reg_bins)
+{
+  if (cgs != HS.next_top) return;
+  rq_start_stats &T = g_rq_start[2 * (l2 - 2) + (color ? 1 : 0)];
+  const int cgw = n >> 2, top = cgs, ftop = scan[top * 16];
+  const int dg = ((ftop & (n - 1)) >> 2) + ((ftop >> l2) >> 2);
+  int ng = top - rdoq_diag_start(cgw, dg) + 1 < 4 ? top - rdoq_diag_start(cgw, dg) + 1 : 4;
+  const bool regular = reg_bins >= 4;
+  bool fast = !regular;
+  if (n == 4) fast = true;                                  // the leaf: always the fixed point
+  else if (regular) {
+    int bound[4] = {0, 0, 0, 0};
+    for (int r = 0; r < ng; ++r)
+      for (int k = 0; k < 16; ++k) {
+        const int scanpos = (top - r) * 16 + k;
+        if (scanpos > last_scanpos) continue;
+        const int mal = rq_start_candidate(E, q, coef[scan[scanpos]]).mal;
+        bound[r] += (mal < 2 ? mal : 3) + (scanpos == last_scanpos ? 0 : 1);
+      }
+    fast = (int)reg_bins - (bound[0] + bound[1] + bound[2] + bound[3]) >= 4;
+    if (!fast && ng > 1) { ng = 1; fast = (int)reg_bins - bound[0] >= 4; }
+  }
+  HS.ng = ng; HS.on = fast; HS.next_top = top - ng;
+  if (!fast) { T.slow_groups += 1; return; }
+  int rounds[4] = {0, 0, 0, 0};
+  for (int r = 0; r < ng; ++r) {
+    int16_t start_lv[16], got[16];
+    for (int s = 0; s < 4; ++s) {
+      const int k = rq_start_iterate(E, q, scan, coef, dst, n, l2, color, top - r, last_scanpos, regular, s, s == 0 ? HS.want[r] : got, start_lv);
+      rounds[s] = k > rounds[s] ? k : rounds[s];
+      if (s && memcmp(got, HS.want[r], sizeof got)) T.mismatches += 1;
+      if (s == 1)
+        for (int j = 0; j < 16; ++j) {
+          const int scanpos = (top - r) * 16 + j;
+          if (scanpos > last_scanpos) continue;
+          const int mal = rq_start_candidate(E, q, coef[scan[scanpos]]).mal;
+          if (mal == 1 && scanpos == last_scanpos) T.last_cand1 += 1;
+          if (mal == 1 && start_lv[j] == 0 && got[j] == 1 && scanpos != last_scanpos) T.zero_kept1 += 1;
+          if (mal == 1 && start_lv[j] == 1 && got[j] == 0) T.one_took0 += 1;
+        }
+    }
+  }
+  T.passes += 1;
+  for (int s = 0; s < 4; ++s) T.rounds[s] += rounds[s];
+  T.passes_of[rounds[1] < 3 ? rounds[1] - 1 : 2] += 1;
+}
+// behind a group's positions, before its zero-out: the walk's levels against the iteration's
+inline void rq_start_check(const rq_start_pass &HS, const uint16_t *scan, const int16_t *dst, int l2, int color, int cgs)
+{
+  if (!HS.on) return;
+  const int r = HS.next_top + HS.ng - cgs;
+  for (int k = 0; k < 16; ++k)
+    if (dst[scan[cgs * 16 + k]] != HS.want[r][k]) { g_rq_start[2 * (l2 - 2) + (color ? 1 : 0)].mismatches += 1; return; }
+}
+#endif
 // uvg_rdoq as the reference walks it, of an n x n block (square: no sqrt2 scaling), no LFNST / MTS /
 // sign hiding.  coef -> levels in dst (both n * n, raster).  root_cbf: "no coefficients" of a luma block is priced with the root cbf
 // (a block of an inter CU, rdo.c:1774).  Returns whether any level survived.
@@ -51,8 +194,15 @@ CTU_NOINLINE CTU_DEV int rdoq_serial(const uint8_t *st, const uint16_t *scan, sc
   }
   if (last_scanpos == -1) return 0;
   for (; cgs >= 0; cgs--) cost_cg_sig[cgs] = 0;
+#if defined(CTU_RDOQ_START_STATS)
+  rq_start_pass HS;
+  HS.next_top = cg_last_scanpos; HS.ng = 0; HS.on = 0;
+#endif
 
   for (cgs = cg_last_scanpos; cgs >= 0; cgs--) {
+#if defined(CTU_RDOQ_START_STATS)
+    rq_start_open(HS, E, q, scan, coef, dst, n, l2, color, cgs, last_scanpos, reg_bins);
+#endif
     // the group's raster index = position of its first coefficient / 4
     const int first = scan[cgs * 16];
     const int cg_pos_x = (first & (n - 1)) >> 2, cg_pos_y = (first >> l2) >> 2;
@@ -99,6 +249,9 @@ CTU_NOINLINE CTU_DEV int rdoq_serial(const uint8_t *st, const uint16_t *scan, sc
         if (sp != 0) nnz_before_pos0++;
       }
     }
+#if defined(CTU_RDOQ_START_STATS)
+    rq_start_check(HS, scan, dst, l2, color, cgs);
+#endif
     if (cgs) {
       unsigned right = 0, lower = 0;
       if (cg_pos_x + 1 < cgw) right = cg_flag[cg_blkpos + 1];
