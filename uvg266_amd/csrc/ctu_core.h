@@ -2274,6 +2274,58 @@ template <typename PX> CTU_NOINLINE CTU_DEV void mark_deblocking(lds<PX> *S, int
 // regular bins a scan position spends, from its record (level in bits 0..15, "its sig flag is coded" in bit 29)
 CTU_DEV int rec_spend(uint32_t rec) { const uint32_t a = rec & 0xffffu; return (int)((rec >> 29) & 1u) + (a ? 1 + (a > 1 ? 2 : 0) : 0); }
 
+// ---- the packed sweep's pieces (coeff_bits below, coeff_bits4r in ctu_leaf4.h, the slice coder's model sweep) ----
+// CTX_UPDATE (m_update) on the packed state: both halves shifted by their own window (v_pk_lshrrev_b16); no borrow or carry crosses
+// the halves (a state never exceeds 0x7fe0 / 0x7ffe, what is taken off never the state).  gate: 0x7ffe7fe0 where the model codes
+// the bin, else 0; add: the windows' (0x7fff >> rate) & mask where that bin is 1, else 0.  Host: the two halves one after the other.
+#if defined(__HIPCC__)
+typedef unsigned short cb_u16x2 __attribute__((ext_vector_type(2)));
+CTU_DEV uint32_t cb_step(uint32_t st, uint32_t rpk, uint32_t gate, uint32_t add)
+{
+  const cb_u16x2 sh = __builtin_bit_cast(cb_u16x2, st) >> __builtin_bit_cast(cb_u16x2, rpk);
+  return st - (__builtin_bit_cast(uint32_t, sh) & gate) + add;
+}
+#else
+CTU_DEV uint32_t cb_step(uint32_t st, uint32_t rpk, uint32_t gate, uint32_t add)
+{
+  uint32_t s0 = st & 0xffffu, s1 = st >> 16;
+  s0 = s0 - ((s0 >> (rpk & 0xffffu)) & (gate & 0xffffu)) + (add & 0xffffu);
+  s1 = s1 - ((s1 >> (rpk >> 16)) & (gate >> 16)) + (add >> 16);
+  return (s0 & 0xffffu) | s1 << 16;
+}
+#endif
+// the entropy table's entry of a bin coded with the packed state: (s0 + s1) >> 8 is the model's 8-bit state (m_state)
+CTU_DEV uint32_t cb_idx(uint32_t st, bool one) { return ((((st & 0xffffu) + (st >> 16)) >> 8) << 1) ^ (one ? 1u : 0u); }
+CTU_DEV uint32_t cb_rpk(int rw) { return (uint32_t)(rw >> 4) | (uint32_t)(rw & 15) << 16; }
+CTU_DEV uint32_t cb_addpk(int rw) { return ((0x7fffu >> (rw >> 4)) & 0x7fe0u) | ((0x7fffu >> (rw & 15)) & 0x7ffeu) << 16; }
+
+// A 4x4 block's sweep (coeff_bits4r): plain C++, compiled for the host too (tests/emul_leaf/coeff_bits_keys.cpp replays the sweep).
+// The key word of a position, a byte per role (sig, greater-1, parity, greater-2): context << 1 | bin, 0xff where the position
+// codes no such bin.  a: the absolute level, ctx_sig: its significance context, ofs: its greater-1 context set (0 at the last position),
+// sig_coded: its sig flag is coded (not the last position's), swept: not beyond the last position and not behind the budget's end --
+// a position that is not swept has the key 0xffffffff, which no swept position has (it codes a sig flag or has a level)
+CTU_DEV uint32_t lf4_key(uint32_t a, int ctx_sig, int ofs, bool sig_coded, bool swept)
+{
+  const uint32_t of2 = (uint32_t)ofs << 1;
+  const uint32_t key = (sig_coded ? (uint32_t)ctx_sig << 1 | (a != 0 ? 1u : 0u) : 0xffu) | (a != 0 ? of2 | (a > 1 ? 1u : 0u) : 0xffu) << 8 |
+                       (a > 1 ? of2 | (a & 1u) : 0xffu) << 16 | (a > 1 ? of2 | (a >= 4 ? 1u : 0u) : 0xffu) << 24;
+  return swept ? key : 0xffffffffu;
+}
+// lane -> the model it sweeps: role 0 sig (luma 12, chroma 8 lanes), then 1 greater-1, 2 parity, 3 greater-2 (luma 16, chroma 11
+// lanes each; a 4x4 luma block has the context sets 0 and 6..20), -1: none.  The model codes a bin where the byte of its role is 2 k
+// or 2 k + 1
+struct lf4_owner { int role, k, model; };
+CTU_DEV lf4_owner lf4_lane_model(int lane, int t)
+{
+  const int nk0 = t ? 8 : 12, nks = t ? 11 : 16;
+  lf4_owner o = {-1, 0, 0};
+  if (lane < nk0) { o.role = 0; o.k = lane; }
+  else if (lane < nk0 + 3 * nks) { o.role = 1 + (lane - nk0) / nks; o.k = (lane - nk0) % nks; }
+  if (!t && o.role > 0 && o.k > 0) o.k += 5;
+  o.model = o.role < 0 ? 0 : (o.role == 0 ? M_SIG + 12 * t : o.role == 1 ? M_GT1 + 21 * t : o.role == 2 ? M_PAR + 21 * t : M_GT2 + 21 * t) + o.k;
+  return o;
+}
+
 #if defined(__HIPCC__)
 #include "ctu_leaf4.h"
 #endif
@@ -2296,21 +2348,6 @@ CTU_DEV int rec_spend(uint32_t rec) { const uint32_t a = rec & 0xffffu; return (
 // All 64 lanes of wave 0 call it; the returned value is the same on every lane.  Host emulation: the serial walk.
 // BITS = false: the models' adaptation only (the coder's pass: nobody reads the count; returns 0): the same steps without the Rice
 // parameters, the entropy-table lookups, the bypass pass and the sums.
-#if defined(__HIPCC__)
-typedef unsigned short cb_u16x2 __attribute__((ext_vector_type(2)));
-// CTX_UPDATE (m_update) on the packed state: both halves shifted by their own window (v_pk_lshrrev_b16); no borrow or carry crosses
-// the halves (a state never exceeds 0x7fe0 / 0x7ffe, what is taken off never the state).  gate: 0x7ffe7fe0 where the model codes
-// the bin, else 0; add: the windows' (0x7fff >> rate) & mask where that bin is 1, else 0
-CTU_DEV uint32_t cb_step(uint32_t st, uint32_t rpk, uint32_t gate, uint32_t add)
-{
-  const cb_u16x2 sh = __builtin_bit_cast(cb_u16x2, st) >> __builtin_bit_cast(cb_u16x2, rpk);
-  return st - (__builtin_bit_cast(uint32_t, sh) & gate) + add;
-}
-// the entropy table's entry of a bin coded with the packed state: (s0 + s1) >> 8 is the model's 8-bit state (m_state)
-CTU_DEV uint32_t cb_idx(uint32_t st, bool one) { return ((((st & 0xffffu) + (st >> 16)) >> 8) << 1) ^ (one ? 1u : 0u); }
-CTU_DEV uint32_t cb_rpk(int rw) { return (uint32_t)(rw >> 4) | (uint32_t)(rw & 15) << 16; }
-CTU_DEV uint32_t cb_addpk(int rw) { return ((0x7fffu >> (rw >> 4)) & 0x7fe0u) | ((0x7fffu >> (rw & 15)) & 0x7ffeu) << 16; }
-#endif
 template <typename PX, bool BITS = true> CTU_NOINLINE CTU_DEV double coeff_bits(lds<PX> *S, uint32_t *m_, int update, const int16_t *coeff_, int n, int color)
 {
   wctx *const V = wv_of(S);

@@ -330,8 +330,13 @@ CTU_DEV void lf_luma_mode_bits(uint32_t *m_, const int (&p)[6], int mode, double
 // ---- coefficient bit cost of a 4x4 block -------------------------------------------------------------------------------------------
 // coeff_bits (ctu_core.h) for the one coefficient group of a 4x4 block, in RASTER order over the lanes 0..15 (`lev`: the signed level
 // of position lane & 15; every row of 16 lanes may repeat it): the context template's neighbours are DPP row shifts, what is counted along the scan reads the
-// owners' registers in scan order, and the entropy-table lookups are taken out of the adaptation chain (a model's state after a bin
-// does not depend on the bin's cost): the sixteen steps of the sweep are pure register arithmetic, the sixteen lookups go out together.
+// owners' registers in scan order.  The sweep is coeff_bits' packed one (ctu_core.h): the sixteen position lanes pack a key word each
+// (lf4_key: the sig / greater-1 / parity / greater-2 bytes, 0xffffffff beyond the last position and behind the budget's end), every
+// model lives in a lane (lf4_lane_model) as a packed state, and a step is a byte compare and one cb_step; a bin's entropy-table
+// lookup goes out in its step and is added in the next step that runs (a model's state after a bin does not depend on the bin's cost).
+// The key word of a step comes by v_readlane, not by the row broadcast (lf_rb): it is the same for the whole wave, so the skip of a
+// step is a scalar compare and branch on it, the byte extraction's operand is a scalar register, and the rows above the first need
+// not hold the levels.
 // Same bins, same adaptation, same sum as uvg_encode_coeff_nxn in count mode (encode_coding_tree-generic.c:53-323).
 // BITS = false: the models' adaptation only (the coder's pass: nobody reads the count) -- no entropy-table lookups, no Rice
 // parameters, no bypass bits, no sums.
@@ -348,12 +353,8 @@ template <typename PX, bool BITS = true> CTU_DEV double coeff_bits4r(lds<PX> *S,
   const int last_lane = __builtin_ctzll(__ballot(is_last));
   const int last = __builtin_amdgcn_readlane(sp, last_lane);           // scan index of the last significant position
   // this lane's models: the sweep's (one per lane, 12 + 3 * 16 luma / 8 + 3 * 11 chroma) and, lanes 0..5, a last-position prefix model
-  const int nk0 = t ? 8 : 12, nks = t ? 11 : 16;
-  int role = -1, k = 0;
-  if (lane < nk0) { role = 0; k = lane; }
-  else if (lane < nk0 + 3 * nks) { role = 1 + (lane - nk0) / nks; k = (lane - nk0) % nks; }
-  if (!t && role > 0 && k > 0) k += 5;          // 4x4 luma: set offsets 0, 6..20
-  const int model = role < 0 ? 0 : (role == 0 ? M_SIG + 12 * t : role == 1 ? M_GT1 + 21 * t : role == 2 ? M_PAR + 21 * t : M_GT2 + 21 * t) + k;
+  const lf4_owner own = lf4_lane_model(lane, t);
+  const int role = own.role, k = own.k, model = own.model;
   const int paxis = lane >= 3, pq = lane - 3 * paxis;                // prefix: lanes 0..2 x, 3..5 y; a 4x4 block: offset 0, shift 0, three models per axis
   const int pmodel = (paxis ? M_LASTY : M_LASTX) + 20 * t + (lane < 6 ? pq : 0);
   uint32_t st = m[model];
@@ -383,7 +384,6 @@ template <typename PX, bool BITS = true> CTU_DEV double coeff_bits4r(lds<PX> *S,
   const bool live = sp <= last;
   const int sig_coded = live && sp != last;
   const int spend = live ? sig_coded + (a ? 1 + (a > 1 ? 2 : 0) : 0) : 0;
-  const uint32_t rec = (uint32_t)(a > 0xffff ? 0xffff : a) | (uint32_t)ctx_sig << 16 | (uint32_t)ofs << 20 | (uint32_t)sig_coded << 29;
   // where the regular-bin budget (28 for 16 coefficients) runs out: scan positions <= sw are bypass-coded
   const int tot = __popc((unsigned)__ballot(spend & 1) & 0xffffu) + 2 * __popc((unsigned)__ballot(spend & 2) & 0xffffu) + 4 * __popc((unsigned)__ballot(spend & 4) & 0xffffu);
   int sw = -1;
@@ -394,62 +394,37 @@ template <typename PX, bool BITS = true> CTU_DEV double coeff_bits4r(lds<PX> *S,
       rb -= __builtin_amdgcn_readlane(spend, LF_SCAN(j));
     }
   }
-  // ---- the sweep: every model along the positions in coding order; states only ----
-  const int r0w = rw >> 4, r1w = rw & 15;
-  const uint32_t add0 = (0x7fffu >> r0w) & 0x7fe0u, add1 = (0x7fffu >> r1w) & 0x7ffeu;
-  const uint32_t fsh = role == 0 ? 16 : 20, fmask = role == 0 ? 15u : 31u, rsel = role < 0 ? 31u : (uint32_t)role;
-  uint32_t idx[16];
-  uint32_t hits = 0;
+  CTU_LDS const uint32_t *const ebits = LDSP(const uint32_t, tab_ebits());
+  (void)ebits;
+  const uint32_t kGate = 0x7ffe7fe0u;
+  uint32_t acc = 0;                   // BITS: the costs of the bins this lane's models code, in units of 2^-15
+  // ---- the last-position prefix (uvg_encode_last_significant_xy, :415-470): model q of an axis sees one bin at most -- 1 below the
+  // position's coordinate, 0 at it (none at 3).  Its lookup is in flight during the sweep
+  const int last_r = LF_SCAN(last), pos = paxis ? last_r >> 2 : last_r & 3;
+  const bool phit = lane < 6 && pq <= pos && pq < 3, pone = pq < pos;
+  uint32_t ppc = 0;
+  if constexpr (BITS) ppc = ebits[cb_idx(pst, pone)];
+  if (phit && update) m[pmodel] = cb_step(pst, cb_rpk(prw), kGate, pone ? cb_addpk(prw) : 0u);
+  // ---- the sweep: every model along the positions in coding order.  A bin costs ebits[] of its model's state BEFORE the step: the
+  // lookup goes out in the step and is added in the next step that runs (pc, gated by ph: the lane's model coded the bin) ----
+  {
+    const uint32_t keys = lf4_key((uint32_t)(a > 0xffff ? 0xffff : a), ctx_sig, ofs, sig_coded != 0, live && sp > sw);
+    const uint32_t rpk = cb_rpk(rw), addpk = cb_addpk(rw);
+    const uint32_t sh8 = role < 0 ? 0u : (uint32_t)role * 8u, k2 = role < 0 ? 0x1000u : (uint32_t)k << 1;
+    uint32_t pc = 0;
+    bool ph = false;
 #pragma unroll
-  for (int j = 15; j >= 0; --j) {
-    idx[j] = 0;
-    if (j > last || j <= sw) continue;              // (wave-uniform: the steps beyond the last position / behind the budget's end cost nothing)
-    const uint32_t rj = (uint32_t)__builtin_amdgcn_readlane((int)rec, LF_SCAN(j));
-    const uint32_t aj = rj & 0xffffu;
-    // per role (sig, gt1, parity, gt2): does the position code a bin with one of the role's models, and which
-    const uint32_t gates = ((rj >> 29) & 1u) | (aj != 0 ? 2u : 0u) | (aj > 1 ? 12u : 0u);
-    if (gates == 0) continue;
-    const uint32_t bins = (aj != 0 ? 1u : 0u) | (aj > 1 ? 2u : 0u) | ((aj & 1u) << 2) | (aj >= 4 ? 8u : 0u);
-    const bool hit = ((gates >> rsel) & 1u) && ((rj >> fsh) & fmask) == (uint32_t)k;
-    const uint32_t bin = (bins >> rsel) & 1u;
-    uint32_t s0 = st & 0xffffu, s1 = st >> 16;
-    if (BITS) idx[j] = (((s0 + s1) >> 8) << 1) ^ bin;
-    s0 -= (s0 >> r0w) & 0x7fe0u;
-    s1 -= (s1 >> r1w) & 0x7ffeu;
-    s0 += bin ? add0 : 0u;
-    s1 += bin ? add1 : 0u;
-    st = hit ? ((s0 & 0xffffu) | (s1 << 16)) : st;
-    hits |= hit ? 1u << j : 0u;
+    for (int j = 15; j >= 0; --j) {
+      const uint32_t kj = (uint32_t)__builtin_amdgcn_readlane((int)keys, LF_SCAN(j));
+      if (kj == 0xffffffffu) continue;                // (wave-uniform: beyond the last position / behind the budget's end)
+      const uint32_t d = ((kj >> sh8) & 0xffu) - k2;
+      if constexpr (BITS) { acc += ph ? pc : 0u; pc = ebits[cb_idx(st, d == 1u)]; ph = d < 2u; }
+      st = cb_step(st, rpk, d < 2u ? kGate : 0u, d == 1u ? addpk : 0u);
+    }
+    if constexpr (BITS) acc += (ph ? pc : 0u) + (phit ? ppc : 0u);
   }
   if (role >= 0 && update) m[model] = st;
-  // the last-position prefix (uvg_encode_last_significant_xy, :415-470): model q of an axis sees one bin at most -- 1 below the
-  // position's coordinate, 0 at it (none at 3)
-  const int last_r = LF_SCAN(last), pos = paxis ? last_r >> 2 : last_r & 3;
-  const bool phit = lane < 6 && pq <= pos && pq < 3;
-  const uint32_t pbin = pq < pos ? 1u : 0u;
-  uint32_t pidx;
-  {
-    uint32_t s0 = pst & 0xffffu, s1 = pst >> 16;
-    pidx = (((s0 + s1) >> 8) << 1) ^ pbin;
-    const int p0w = prw >> 4, p1w = prw & 15;
-    s0 -= (s0 >> p0w) & 0x7fe0u;
-    s1 -= (s1 >> p1w) & 0x7ffeu;
-    if (pbin) { s0 += (0x7fffu >> p0w) & 0x7fe0u; s1 += (0x7fffu >> p1w) & 0x7ffeu; }
-    if (phit && update) m[pmodel] = (s0 & 0xffffu) | (s1 << 16);
-  }
-  if (!BITS) { CTU_SYNC(); return 0.0; }
-  // ---- the bins' costs, all lookups in flight together ----
-  CTU_LDS const uint32_t *const ebits = LDSP(const uint32_t, tab_ebits());
-  uint32_t acc = 0;
-  {
-    uint32_t c[16];
-    const uint32_t pc = ebits[pidx];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) { c[j] = 0; if (j <= last && j > sw) c[j] = ebits[idx[j]]; }
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc += (hits >> j) & 1u ? c[j] : 0u;
-    acc += phit ? pc : 0u;
-  }
+  if constexpr (!BITS) { CTU_SYNC(); return 0.0; }
   // ---- bypass-coded parts: remainders, bypass positions, signs ----
   int ibits = 0;
   if (lane < 16 && live) {
