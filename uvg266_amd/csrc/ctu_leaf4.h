@@ -19,7 +19,7 @@
 //     population count over the positions later in scan order, and the positions are decided together by the fixed-point iteration
 //     of rdoq_wave, which here also covers the blocks where the budget runs out (a position's "regular" flag is a function of the
 //     levels later in scan order, like its contexts: same DAG);  the sums the reference forms in scan order are formed from the
-//     owners' registers with v_readlane in that order;
+//     owners' registers with v_readlane in that order, and the last-position search runs down the lanes (lf_last_search);
 //   * blocks that do not wait for each other -- the Cb and Cr blocks of an 8x8 area and the luma block of the 4x4 CU that carries
 //     them -- go through these steps together, a block per row of 16 lanes (leaf_recon_rows).
 // Device only (the host emulation keeps the general path: the two agree only if this reformulation is right; the GPU tests hold the
@@ -632,6 +632,52 @@ CTU_DEV int lf_inv_pass(int v, int shift)
 }
 
 // ---- uvg_rdoq for a 4x4 block ----------------------------------------------------------------------------------------------------
+// The last-position search of a 4x4 block (rdo.c:1805-1825) down the lanes of its row of 16: rdoq_wave's form (ctu_core.h, there
+// with the argument) for the one group a 4x4 block is.  The lanes hold the block in raster order, so the five operands -- the level,
+// what a step takes from base_cost (kx) and gives back (k0), the position's bits and the significance flag's cost -- first come
+// into scan order: lane k of a row takes raster lane LF_SCAN(k)'s.  Lane k then holds base_cost as step k finds it (before) and
+// leaves it ((before - kx) + k0), `before` coming down from lane k + 1 a lane a round: the shift stays inside the row (row_shl:1) and
+// lane 15, which has no source, keeps the incoming base_cost -- the rows above are blocks of their own, or copies.  The sixteen
+// totals are formed once, each in its lane; the choice among the candidates (the levels from the highest level above 1 up: the walk
+// ends there) is rq_last_lower over the row, then rq_last_pick.  A position beyond the last candidate holds level 0, kx = k0 = +0.0:
+// base_cost passes it unchanged and it is no candidate.  ROWS: a block per row (the ballots are the row's); otherwise every row
+// repeats one block and the masks are scalars.  -> best_last_idx_p1 of the lane's row, in every lane of the row.
+// Callers: all 64 lanes active (DPP and ds_bpermute read +0.0 from an inactive lane, not its value); base_cost and best_cost the
+// same in every lane of a row.
+template <int CTRL> CTU_DEV double lf_dpp64_keep(double v, double keep)       // dpp64, but a lane without a source reads `keep`
+{
+  const int lo = __builtin_amdgcn_update_dpp(__double2loint(keep), __double2loint(v), CTRL, 0xf, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(keep), __double2hiint(v), CTRL, 0xf, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+CTU_DEV double lf_shfl64(double v, int src_lane) { return __hiloint2double(lf_shfl(__double2hiint(v), src_lane), lf_shfl(__double2loint(v), src_lane)); }
+// the ballot of the lane's own row
+CTU_DEV unsigned lf_row_ballot(bool p) { return (unsigned)(__ballot(p) >> (CTU_TID & 48)) & 0xffffu; }
+template <bool ROWS> CTU_DEV unsigned lf_ballot16(bool p) { return ROWS ? lf_row_ballot(p) : (unsigned)__ballot(p) & 0xffffu; }
+template <bool ROWS> CTU_DEV int lf_last_search(int lev, double cc, double c0, double cs, double klast, double base_cost, double best_cost)
+{
+  const int lane = CTU_TID, k = lane & 15, from = (lane & 48) + LF_SCAN(k);
+  const int klev = lf_shfl(lev, from);
+  const double kx = lf_shfl64(lev ? cc : cs, from), k0 = lf_shfl64(lev ? c0 : 0.0, from), kl = lf_shfl64(klast, from), kcs = lf_shfl64(cs, from);
+  const unsigned m_nz = lf_ballot16<ROWS>(klev != 0), m_gt1 = lf_ballot16<ROWS>(klev > 1);
+  const int kstop = m_gt1 ? 31 - __clz(m_gt1) : 0;
+  const unsigned cand = m_nz >> kstop << kstop;
+  double before = base_cost, after = base_cost - kx + k0;
+#pragma unroll
+  for (int i = 0; i < 15; ++i) {
+    before = lf_dpp64_keep<0x101>(after, base_cost);                // row_shl:1
+    after = before - kx + k0;
+  }
+  const double total = before + kl - kcs;
+  const bool is_cand = (cand >> k & 1u) != 0;
+  double m = is_cand ? total : best_cost;
+  m = rq_last_lower(m, dpp64<0xB1>(m));                             // quad_perm [1,0,3,2]
+  m = rq_last_lower(m, dpp64<0x4E>(m));                             // quad_perm [2,3,0,1]
+  m = rq_last_lower(m, dpp64<0x141>(m));                            // row_half_mirror
+  m = rq_last_lower(m, dpp64<0x140>(m));                            // row_mirror: every lane of the row has the row's minimum
+  return rq_last_pick(m, lf_ballot16<ROWS>(is_cand && total == m), best_cost);
+}
+
 // coef: lane r (raster; every row of 16 lanes repeats) holds coefficient r.  Returns the level of position r with its sign (0 beyond
 // the chosen last position); *has_out = any level survived (wave-uniform).
 template <typename PX> CTU_DEV int leaf_rdoq(lds<PX> *S, int coef, int color, int cbf_u, int qp_scaled, double lambda, int *has_out)
@@ -661,11 +707,11 @@ template <typename PX> CTU_DEV int leaf_rdoq(lds<PX> *S, int coef, int color, in
   const int last_lane = __builtin_ctzll(__ballot(is_last));
   const int last_sp = __builtin_amdgcn_readlane(sp, last_lane);
   const bool mine = sp <= last_sp;
-  // the positions behind the last candidate only add their level-0 cost (rdo.c:1556-1583), in descending scan order
-  double block_uncoded_cost = 0, base_cost = 0;
+  // block_uncoded_cost: every position's level-0 cost in descending scan order, behind the last candidate (rdo.c:1556-1583) and up
+  // to it (rdo.c:1689-1772) alike -- one sum from +0.0, no test of last_sp; it needs nothing of the fixed point and stands in front of it
+  double block_uncoded_cost = 0;
 #pragma unroll
-  for (int k = 15; k >= 1; --k)
-    if (k > last_sp) { const double c = rl64(c0, LF_SCAN(k)); block_uncoded_cost += c; base_cost += c; }
+  for (int k = 15; k >= 0; --k) block_uncoded_cost += rl64(c0, LF_SCAN(k));
   // the Rice parameter a regular-coded position inherits: from the INPUT coefficients around the position coded before it (rdo.c:1697)
   int go_rice_reg = 0;
   {
@@ -716,13 +762,17 @@ template <typename PX> CTU_DEV int leaf_rdoq(lds<PX> *S, int coef, int color, in
     lev = level;
     if (__ballot(changed) == 0) break;
   }
-  // ---- the sums in scan order (rdo.c:1689-1772; one group: no group decision) ----
+  // ---- the sums in scan order (rdo.c:1556-1583, 1689-1772; one group: no group decision) ----
+  // base_cost: the same walk, a position behind the last candidate giving its level-0 cost, one up to it its coded cost -- the
+  // position's owner chooses, the steps test nothing
+  double base_cost = 0;
+  {
+    const double cb = mine ? cc : c0;
 #pragma unroll
-  for (int k = 15; k >= 0; --k)
-    if (k <= last_sp) { block_uncoded_cost += rl64(c0, LF_SCAN(k)); base_cost += rl64(cc, LF_SCAN(k)); }
+    for (int k = 15; k >= 0; --k) base_cost += rl64(cb, LF_SCAN(k));
+  }
   // ---- coded block flag and the last significant position (rdo.c:1774-1833) ----
   double best_cost;
-  int best_last_idx_p1 = 0;
   {
     const int o_cbf = color == 0 ? M_CBF_LUMA : color == 1 ? M_CBF_CB : M_CBF_CR + (cbf_u ? 1 : 0);
     best_cost = block_uncoded_cost + lambda * rbits(E, o_cbf, 0);
@@ -734,22 +784,7 @@ template <typename PX> CTU_DEV int leaf_rdoq(lds<PX> *S, int coef, int color, in
     const double cl = last_x_bits[px] + last_y_bits[py];
     klast = lambda * cl;
   }
-  bool found_last = false;
-#pragma unroll
-  for (int k = 15; k >= 0; --k) {
-    if (found_last || k > last_sp) continue;
-    const int level = __builtin_amdgcn_readlane(lev, LF_SCAN(k));
-    const double s_ = rl64(cs, LF_SCAN(k));
-    if (level) {
-      const double total = base_cost + rl64(klast, LF_SCAN(k)) - s_;
-      if (total < best_cost) { best_last_idx_p1 = k + 1; best_cost = total; }
-      if (level > 1) { found_last = true; continue; }
-      base_cost -= rl64(cc, LF_SCAN(k));
-      base_cost += rl64(c0, LF_SCAN(k));
-    } else {
-      base_cost -= s_;
-    }
-  }
+  const int best_last_idx_p1 = __builtin_amdgcn_readfirstlane(lf_last_search<false>(lev, cc, c0, cs, klast, base_cost, best_cost));
   *has_out = best_last_idx_p1 > 0;
   return sp < best_last_idx_p1 ? (coef < 0 ? -lev : lev) : 0;
 }
@@ -816,8 +851,7 @@ template <typename PX> CTU_INLINE1 CTU_DEV lf_block leaf_recon_inl(lds<PX> *S, c
 // lane L of the lane's own row of 16 (DPP row_newbcast: every lane of the row is a valid source, the whole wave must be active)
 template <int L> CTU_DEV int lf_rb(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x150 + L, 0xf, 0xf, true); }
 template <int L> CTU_DEV double lf_rb64(double v) { return __hiloint2double(lf_rb<L>(__double2hiint(v)), lf_rb<L>(__double2loint(v))); }
-// the ballot of the lane's own row
-CTU_DEV unsigned lf_row_ballot(bool p) { return (unsigned)(__ballot(p) >> (CTU_TID & 48)) & 0xffffu; }
+// (lf_row_ballot, the ballot of the lane's own row: above, with lf_last_search)
 CTU_DEV int lf_rows_min(int v)
 {
   const int a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16), c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
@@ -924,7 +958,6 @@ template <typename PX> CTU_DEV int leaf_rdoq_rows(lds<PX> *S, int coef, int colo
   }
   // ---- coded block flag and the last significant position (rdo.c:1774-1833) ----
   double best_cost;
-  int best_last_idx_p1 = 0;
   {
     const int o_cbf = color == 0 ? M_CBF_LUMA : color == 1 ? M_CBF_CB : M_CBF_CR + (cbf_u ? 1 : 0);
     best_cost = block_uncoded_cost + lambda * rbits(E, o_cbf, 0);
@@ -936,21 +969,8 @@ template <typename PX> CTU_DEV int leaf_rdoq_rows(lds<PX> *S, int coef, int colo
     const double cl = last_x_bits[px] + last_y_bits[py];
     klast = lambda * cl;
   }
-  // a step of the search: a position with a level is a candidate for the last one and, at level 1, leaves base_cost - cc + c0; one
-  // without leaves base_cost - cs (+ 0.0); the first level above 1 ends the row's search (what base_cost becomes after that, nobody reads)
-  const double sub = lev ? cc : cs, add = lev ? c0 : 0.0;          // (lev, cs: 0 beyond the row's last candidate)
-  bool open = act;                                          // the row's search for the last position still runs
-#define LF_STEP(k) if ((k) <= max_last) { \
-    const int level = lf_rb<LF_SCAN(k)>(lev); \
-    const double total = base_cost + lf_rb64<LF_SCAN(k)>(klast) - lf_rb64<LF_SCAN(k)>(cs); \
-    const bool better = open && level != 0 && total < best_cost; \
-    best_cost = better ? total : best_cost; \
-    best_last_idx_p1 = better ? (k) + 1 : best_last_idx_p1; \
-    base_cost -= lf_rb64<LF_SCAN(k)>(sub); \
-    base_cost += lf_rb64<LF_SCAN(k)>(add); \
-    open = open && level <= 1; }
-  LF_DESC16(LF_STEP)
-#undef LF_STEP
+  // every row's search at once, each down its own lanes (a row without a candidate holds no level: no candidate for the last position)
+  const int best_last_idx_p1 = lf_last_search<true>(lev, cc, c0, cs, klast, base_cost, best_cost);
   const bool has = act && best_last_idx_p1 > 0;
   *has_out = has;
   return has && sp < best_last_idx_p1 ? (coef < 0 ? -lev : lev) : 0;
